@@ -2,7 +2,7 @@
 
     python -m alfalfa_amd.build          # -> alfalfa_amd/lib/libalfalfa_amd.so
 
-hipcc cross-compiles without a GPU.  The .so is git-ignored but travels with gpurun snapshots.
+hipcc cross-compiles without a GPU.  The .so is a build product (git-ignored): build() makes it in every fresh tree.
 """
 import os
 import subprocess

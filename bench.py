@@ -13,9 +13,10 @@ comes from the number of chains in flight.  Key frames are handed to the GPU par
 is reconstructed, inter frames `--depth` steps before -- as far as the HBM budget (`--hbm-gb`) holds what they store; frames
 are released as they are consumed, so memory is a ring.  The timed region runs K steps from an EMPTY pipeline to an EMPTY
 pipeline (it pays for filling and draining); `value` is that end-to-end rate, `steady_state` the rate between fill and drain.
-The LAST step of the timed region is the one whose rasters are compared with the reference decoder.
+The LAST step of the timed region is the one whose rasters are compared with the reference decoder; `--dump-outputs DIR`
+writes them to DIR as .npy files too (dump_outputs), so that two builds run with the same arguments can be compared.
 
-    python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Multi-GPU: one process per GPU, independent streams per rank (weak scaling, no data-path collective); the only RCCL
@@ -32,8 +33,15 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 
 # The pipeline runs 15 HIP streams side by side; HIP multiplexes streams over GPU_MAX_HW_QUEUES (default 4) hardware queues and
-# reads the variable when the runtime starts -- which, with torch.distributed, is before libalfalfa_amd.so is loaded.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# reads the variable when the runtime starts -- which, with torch.distributed, is before libalfalfa_amd.so is loaded.  The benchmark
+# asks for the 16 a context wants (include/alfalfa_amd.h) for its own process whatever the caller's environment says, unless that
+# is 16 or more: the queue count it ran with is in the result line (config.gpu_max_hw_queues).
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES") or 0)
+except ValueError:
+    _queues = 0
+if _queues < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 # the worker waves account for their own time (a few clock reads per 32 decode steps): the entropy decode's own roof in the
 # bench line comes from these counters
 os.environ.setdefault("ALFALFA_AMD_TOKEN_PROFILE", "1")
@@ -116,6 +124,8 @@ def parse_args():
                     "2 pre-pass threads) -- what a rank gets when eight share a 16-CPU grant -- this many steps, reported as per_rank_on_2_cpus (0 = skip)")
     ap.add_argument("--secondary-streams", type=int, default=96)
     ap.add_argument("--secondary-steps", type=int, default=4)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region: write the rasters its last step decoded (every distinct "
+                    "stream, every frame) to DIR/<name>.npy as float32 / float64, at most 64 MB in all (dump_outputs)")
     return ap.parse_args()
 
 
@@ -479,6 +489,54 @@ def verify_against_reference(env, decoders_by_index, paths, frames_to_check):
     return {"streams_checked": len(refs), "frames_per_stream": len(frames_to_check), "bit_exact": True}
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000       # (files on disk, .npy headers included)
+
+
+def dump_outputs(out_dir, env, decoders_by_index, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the timed path handed its caller in its last step -- the decoded rasters (three padded planes per
+    frame) of every distinct stream of that step -- as .npy files in `out_dir`, at most `budget` bytes in all:
+        plane_sums.npy          float64 [stream, frame, plane]  the sum of every byte of each padded plane (every byte counts)
+        last_frame_{y,u,v}.npy  float32 [rows, cols]            the whole padded planes of the first stream's last frame
+        sample_{y,u,v}.npy      float32 [stream, frame, k]      each plane at k positions drawn once with a fixed seed
+    Streams in ascending order of their seed and frames in decode order; the positions depend only on the geometry and the
+    budget, so two builds run with the same arguments write files that compare value for value.  -> summary dict."""
+    import numpy as np
+    order = sorted(decoders_by_index, key=lambda i: env["seeds"][i])
+    n, F = len(order), env["F"]
+    sizes = env["plane_sizes"]
+    fixed = n * F * 3 * 8 + 7 * 128                             # (plane sums + the seven files' .npy headers)
+    whole = 4 * sum(sizes) <= (budget - fixed) // 2             # (the whole last frame takes at most half of what is left)
+    room = budget - fixed - (4 * sum(sizes) if whole else 0)
+    per_frame = max(3, room // (4 * n * F))                     # float32 samples per (stream, frame), shared by the planes by size
+    rng = np.random.default_rng(20261015)
+    picks = [np.sort(rng.choice(sz, size=min(sz, max(1, per_frame * sz // sum(sizes))), replace=False)) for sz in sizes]
+    sums = np.zeros((n, F, 3), np.float64)
+    samples = [np.zeros((n, F, len(p)), np.float32) for p in picks]
+    last = None
+    for a, i in enumerate(order):
+        for f in range(F):
+            planes = decoders_by_index[i].raster(f)
+            for k, pl in enumerate(planes):
+                flat = pl.reshape(-1)
+                sums[a, f, k] = float(flat.sum(dtype=np.int64))
+                samples[k][a, f] = flat[picks[k]]
+            if a == 0 and f == F - 1:
+                last = planes
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"plane_sums": sums}
+    for k, name in enumerate("yuv"):
+        arrays["sample_" + name] = samples[k]
+        if whole:
+            arrays["last_frame_" + name] = last[k].astype(np.float32)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    total = sum(os.path.getsize(os.path.join(out_dir, name + ".npy")) for name in arrays)
+    assert total <= budget, total
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in arrays), "bytes": total, "streams": n, "frames_per_stream": F,
+            "stream_seeds": [env["seeds"][i] for i in order], "samples_per_frame": [len(p) for p in picks],
+            "what": "rasters written by the last step of the timed region"}
+
+
 def make_env(args, ctx, config, S, F, rank, world, threads):
     import alfalfa_amd as aa
     import workload
@@ -819,6 +877,12 @@ def main():
         verified = verify_against_reference(env, {i: kept[i] for i in env["distinct"]}, paths, sorted({0, F // 2, F - 1}))
         if verified:
             verified["what"] = "rasters written by the last step of the timed region"
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        if not kept:
+            raise SystemExit("--dump-outputs: the last timed step kept no rasters")
+        dumped = dump_outputs(args.dump_outputs, env, {i: kept[i] for i in env["distinct"]})
+        log("outputs of the last timed step: %d bytes in %s" % (dumped["bytes"], dumped["dir"]))
     del kept
 
     log("verified: %s" % (verified,))
@@ -1092,7 +1156,8 @@ def main():
                        "compressed_bytes_per_mb": round(compressed_bytes / mbs_per_step, 2), "sharding": "streams, one shard per GPU, no data-path collective",
                        "schedule": args.schedule, "key_frames_ahead": pipe_K, "inter_frames_ahead": pipe_D, "inter_headers_ahead_of_tokens": args.header_ahead, "host_threads": threads,
                        "hbm_budget_gb": round(hbm_budget / 1e9, 1), "look_ahead_if_memory_were_free_gb": planned_need_gb, "hbm_taken_by_the_context_gb": memory["hbm_taken_by_the_context_gb"],
-                       "coefficient_storage": "packed" if info["packed_coefficients"] else "dense"},
+                       "coefficient_storage": "packed" if info["packed_coefficients"] else "dense",
+                       "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "stream_concurrency": info.get("stream_concurrency")},
             "memory": memory, "entropy_decode_roof": lanes_roof, "delivery": delivery, "macroblocks_parsed_whole_run": mbs_whole_run,
             "roofline": roofline, "cpu_baseline": cpu_baseline,
             "kernels": roofs, "units_per_step": units, "launches_per_step": launches_per_step, "device_half": device_half,
@@ -1113,6 +1178,7 @@ def main():
                                    "all_frames_on_gpu_lanes is the same workload with host_share_ms = 0"},
             "host": {"parser_mb_per_s_per_core": round(parser_only, 1), "stream_generation_s": round(t_gen, 1)},
             "kernel_stats": kstats, "verified_bit_exact_vs_reference": verified, "verified_profile_step": verified_profile_step, "entry_state_handoff": handoff,
+            "dumped_outputs": dumped,
         }
     else:
         line = None

@@ -5,7 +5,17 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# A decoder context runs 16 HIP streams and wants a hardware queue for each (include/alfalfa_amd.h, aa_runtime_prepare); the
+# library keeps whatever value the environment already has.  The suite asks for 16 for itself -- before anything in this process
+# starts HIP -- and the programs it starts (bench.py, the C++ callers) inherit it.  A value of 16 or more stands.
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES") or 0)
+except ValueError:
+    _queues = 0
+if _queues < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
+
+ROOT =os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)

@@ -183,3 +183,87 @@ def test_calibration_runs_against_a_fake_context(bench, monkeypatch):
            "raster_bytes": 64 * 64 * 3 // 2, "args": args}
     bench.calibrate(env, streams)
     assert ctx.calls == 2 and env["urgent_groups"] == 0 and env["urgent_keys_on_host"] is False and env["urgent_host_estimate_ms"] > 2800
+
+
+def test_dump_outputs_writes_the_kept_rasters_inside_the_budget(bench, tmp_path):
+    """--dump-outputs: plane sums of every frame, the whole last frame of the first stream, and samples at seeded positions -- float32 /
+    float64, inside the budget, and the same files for the same rasters."""
+    import numpy as np
+    pw, ph, F = 64, 48, 3
+
+    class RasterDecoder:
+        padded_width, padded_height = pw, ph
+
+        def __init__(self, seed):
+            self.seed = seed
+
+        def raster(self, f):
+            rng = np.random.default_rng(self.seed * 10 + f)
+            return (rng.integers(0, 256, (ph, pw), dtype=np.uint8), rng.integers(0, 256, (ph // 2, pw // 2), dtype=np.uint8),
+                    rng.integers(0, 256, (ph // 2, pw // 2), dtype=np.uint8))
+    seeds = [101, 100, 101, 102]
+    env = {"F": F, "seeds": seeds, "plane_sizes": (pw * ph, pw * ph // 4, pw * ph // 4)}
+    decs = {1: RasterDecoder(100), 0: RasterDecoder(101), 3: RasterDecoder(102)}
+    budget = 64 << 10
+    a = bench.dump_outputs(str(tmp_path / "a"), env, decs, budget=budget)
+    b = bench.dump_outputs(str(tmp_path / "b"), env, decs, budget=budget)
+    assert a["stream_seeds"] == [100, 101, 102] and a["bytes"] <= budget
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == a["files"] == sorted(["plane_sums.npy", "sample_y.npy", "sample_u.npy", "sample_v.npy", "last_frame_y.npy", "last_frame_u.npy", "last_frame_v.npy"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) == a["bytes"]      # (files on disk, .npy headers included)
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    sums = np.load(tmp_path / "a" / "plane_sums.npy")
+    assert sums.shape == (3, F, 3)
+    for s, i in enumerate([1, 0, 3]):
+        for f in range(F):
+            assert list(sums[s, f]) == [float(p.sum()) for p in decs[i].raster(f)]
+    y, u = decs[1].raster(F - 1)[:2]
+    assert np.array_equal(np.load(tmp_path / "a" / "last_frame_y.npy"), y) and np.array_equal(np.load(tmp_path / "a" / "last_frame_u.npy"), u)
+    sy = np.load(tmp_path / "a" / "sample_y.npy")
+    assert sy.shape[:2] == (3, F) and 0 < sy.shape[2] <= pw * ph
+    assert set(np.unique(sy[2, 1])) <= set(np.unique(decs[3].raster(1)[0]))
+
+
+def test_dump_outputs_samples_the_same_sorted_positions_of_every_plane(bench, tmp_path):
+    """At a budget that forces sampling, every row of sample_{y,u,v} is its own plane (stream, frame, plane) read at one sorted set of
+    distinct positions, the same for every stream and frame: each plane here is a different permutation of 0..size-1, so a value says
+    which position it was read at."""
+    import numpy as np
+    pw, ph, F = 16, 16, 3
+    sizes = (pw * ph, pw * ph // 4, pw * ph // 4)
+    perms = {}
+
+    class PermDecoder:
+        padded_width, padded_height = pw, ph
+
+        def __init__(self, seed):
+            self.seed = seed
+
+        def raster(self, f):
+            out = []
+            for k, (sz, shape) in enumerate(zip(sizes, [(ph, pw), (ph // 2, pw // 2), (ph // 2, pw // 2)])):
+                p = perms.setdefault((self.seed, f, k), np.random.default_rng(self.seed * 100 + f * 10 + k).permutation(sz).astype(np.uint8))
+                out.append(p.reshape(shape))
+            return tuple(out)
+    seeds = [102, 100, 101]
+    env = {"F": F, "seeds": seeds, "plane_sizes": sizes}
+    decs = {i: PermDecoder(sd) for i, sd in enumerate(seeds)}
+    # plane sums + headers, the whole last frame, and 48 samples per (stream, frame): 32 of y, 8 of u, 8 of v
+    budget = (3 * F * 3 * 8 + 7 * 128) + 4 * sum(sizes) + 4 * 3 * F * 48
+    d = bench.dump_outputs(str(tmp_path), env, decs, budget=budget)
+    assert d["samples_per_frame"] == [32, 8, 8] and d["bytes"] <= budget
+    order = sorted(decs, key=lambda i: seeds[i])                  # streams by seed
+    for k, name in enumerate("yuv"):
+        s = np.load(tmp_path / ("sample_%s.npy" % name))
+        assert s.shape == (3, F, d["samples_per_frame"][k])
+        positions = None
+        for a, i in enumerate(order):
+            for f in range(F):
+                inv = np.argsort(perms[(seeds[i], f, k)])                # value -> position in this plane
+                pos = inv[s[a, f].astype(np.int64)]
+                assert (np.diff(pos) > 0).all(), (name, a, f)            # sorted, distinct
+                positions = pos if positions is None else positions
+                assert np.array_equal(pos, positions), (name, a, f)      # the same positions everywhere
+                assert np.array_equal(s[a, f], decs[i].raster(f)[k].reshape(-1)[pos])

@@ -85,12 +85,9 @@ def test_a_four_partition_1080p_key_frame_is_parsed_faster_by_four_lanes():
     """latency of a 4-partition 1080p key frame <= 0.35 x the single-lane figure (the wave simulation said
     0.29-0.31).  Measured on lone chains: nothing else on the GPU."""
     import check_lane_per_partition as clp
+    import workload
     from ivf_io import read_ivf
-    path = os.path.join(ROOT, "gpurun_in", "streams", "1080p_inter_lf_subpel_f6_s100.ivf")
-    if os.path.exists(path):
-        key = read_ivf(path)[2][0]                           # (four partitions, B_PRED and 16x16 intra macroblocks: tools/vp8_synth.perf_stream)
-    else:
-        key = clp.partitioned_stream(1920, 1080, 7, 2, frames=1, density=0.5)[0]
+    key = read_ivf(workload.make_stream("1080p_inter_lf_subpel", 6, 100))[2][0]   # (four partitions, B_PRED and 16x16 intra macroblocks: tools/vp8_synth.perf_stream)
     one, per = aa.Context(0), aa.Context(0)
     per.set_lane_per_partition(True)
     for c in (one, per):
@@ -103,17 +100,14 @@ def test_a_four_partition_1080p_key_frame_is_parsed_faster_by_four_lanes():
 
 @pytest.mark.parametrize("packed", [True, False], ids=["packed", "dense"])
 def test_1080p_four_partition_streams_bit_exact_with_a_lane_per_partition(packed, tmp_path):
-    """The configuration the switch exists for, checked bit for bit with it ON: the shipped `1080p_inter_lf_subpel` streams (1920x1080,
+    """The configuration the switch exists for, checked bit for bit with it ON: the bench's `1080p_inter_lf_subpel` streams (1920x1080,
     four DCT partitions, quarter-pel vectors, SPLITMV, golden / altref; 8 streams x 6 frames, replicated so that waves carry several
     frames and single-lane leftovers side by side) against the REFERENCE decoder (oracle/_ref/ref_decode) where it is built, else the
     oracle -- both coefficient formats; and the frames really took a lane per partition."""
-    import glob
     import hashlib
     import subprocess
-    paths = sorted(glob.glob(os.path.join(ROOT, "gpurun_in", "streams", "1080p_inter_lf_subpel_f6_s*.ivf")))
-    if not paths:
-        import workload
-        paths = workload.make_streams("1080p_inter_lf_subpel", 6, list(range(100, 104)))
+    import workload
+    paths = workload.make_streams("1080p_inter_lf_subpel", 6, list(range(100, 108)))
     ref_decode = os.path.join(ROOT, "oracle", "_ref", "ref_decode")
     want = []
     for p in paths:

@@ -1,8 +1,9 @@
 """The drop-in boundary, tested with the reference's OWN callers: src/tests/decode-to-stdout.cc (its golden-test driver),
 frontend/vp8decode.cc and frontend/decode-bundle.cc are compiled UNMODIFIED -- read from /root/reference at build time,
 never copied -- against include/alfalfa_amd/compat/ (headers with the reference's names), -Wall -Wextra -Werror, and
-linked to the MI355X library.  Builds happen where the reference is (this container; __graft_entry__.build() too); the
-binaries travel to the GPU box under tests/cpp/_build/ like the other built artefacts."""
+linked to the MI355X library.  Builds happen where the reference is (`make -C oracle callers`, which __graft_entry__.build()
+runs too); the binaries go to oracle/_ref/callers/ beside the other binaries built from the reference, and find the library
+relative to themselves, so a tree built where the reference is runs them wherever it is copied."""
 import hashlib
 import os
 import subprocess
@@ -14,24 +15,20 @@ from test_cpp_mirror import _write_ivf, y4m_payload
 
 REF = "/root/reference/src"
 BUILD = os.path.join(ROOT, "tests", "cpp", "_build", "ref_callers")
-CALLERS = {"decode-to-stdout": "tests/decode-to-stdout.cc", "vp8decode": "frontend/vp8decode.cc", "xc-decode-bundle": "frontend/decode-bundle.cc",
-           "xc-dump": "frontend/xc-dump.cc"}
+CALLERS_DIR = os.path.join(ROOT, "oracle", "_ref", "callers")
+CALLERS = ("decode-to-stdout", "vp8decode", "xc-decode-bundle", "xc-dump")     # (their sources: oracle/Makefile, target `callers`)
 
 
 def build_callers():
-    """-> {name: path}.  Rebuilds where the reference sources are; otherwise uses what was built before."""
+    """-> {name: path}.  Rebuilds where the reference sources are (oracle/Makefile, target `callers`); otherwise uses what was
+    built before."""
     from alfalfa_amd import build as b
     b.build()
-    os.makedirs(BUILD, exist_ok=True)
-    libdir = os.path.dirname(b.LIB)
+    if os.path.isdir(REF):
+        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "callers", "R=" + REF], check=True)
     out = {}
-    for name, rel in CALLERS.items():
-        exe, src = os.path.join(BUILD, name), os.path.join(REF, rel)
-        if os.path.exists(src):
-            hdr = os.path.join(ROOT, "include", "alfalfa_amd", "alfalfa.hh")
-            if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(hdr), os.path.getmtime(b.LIB)):
-                subprocess.run(["g++", "-std=c++14", "-O2", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include", "alfalfa_amd", "compat"),
-                                src, "-o", exe, "-L" + libdir, "-lalfalfa_amd", "-Wl,-rpath," + libdir], check=True)
+    for name in CALLERS:
+        exe = os.path.join(CALLERS_DIR, name)
         if os.path.exists(exe):
             out[name] = exe
     return out
