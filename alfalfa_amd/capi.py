@@ -67,6 +67,13 @@ class CtxInfo(C.Structure):
         ("host_waited_parse_ms", C.c_uint32), ("host_waited_compute_ms", C.c_uint32)]
 
 
+AA_RGB_U8_HWC3, AA_RGB_U8_HWC4, AA_RGB_U8_CHW, AA_RGB_F16_CHW, AA_RGB_BF16_CHW, AA_RGB_F32_CHW = range(6)
+
+
+class RgbTarget(C.Structure):
+    _fields_ = [("dst", C.c_void_p), ("row_stride", C.c_int64), ("plane_stride", C.c_int64)]
+
+
 class AlfalfaError(RuntimeError):
     """Mirrors the reference's exception types (exception.hh:76-98) by name in `.kind`."""
 
@@ -119,6 +126,8 @@ SYMBOLS = [
     ("aa_stream_download_async", C.c_int, [_P, C.c_int, _P, _P, _P]), ("aa_stream_download_wait", C.c_int, [_P]),
     ("aa_download_batch_async", C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), _P, C.c_size_t]), ("aa_ctx_download_wait", C.c_int, [_P]), ("aa_ctx_download_wait_until", C.c_int, [_P, C.c_int]),
     ("aa_stream_raster_device", C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    ("aa_render_rgb_async", C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(RgbTarget),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     ("aa_stream_references", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("aa_stream_reference_slots", C.c_int, [_P, C.POINTER(C.c_int)]),
     ("aa_stream_import_reference", C.c_int, [_P, _P, _P, _P]),
@@ -150,6 +159,14 @@ def lib():
                 _build.build()
             elif not os.path.exists(path):
                 raise RuntimeError("libalfalfa_amd.so is missing and hipcc is not available: there is no CPU fallback")
+        # One HIP runtime per process: torch's HIP libraries ask for libamdhip64.so / libhsa-runtime64.so by these bare names and
+        # would start a second runtime of their own beside ours (whose loader names are versioned) -- one that then finds no GPU.
+        # Loaded under these names first, they are the ones a torch imported later binds to (or torch's, if it came first).
+        for name in ("libhsa-runtime64.so", "libamdhip64.so"):
+            try:
+                C.CDLL(name, mode=C.RTLD_GLOBAL)
+            except OSError:
+                pass
         L = C.CDLL(path)
         for name, restype, argtypes in SYMBOLS:
             fn = getattr(L, name)          # AttributeError if the symbol is not exported

@@ -38,6 +38,17 @@ struct aa_gather_job {
   size_t bytes;
 };
 
+// One frame on its way to RGB (aa_render_rgb_async): the display rectangle of a raster -> a caller's device buffer
+struct aa_rgb_job {
+  const uint8_t * plane[3];    // Y, U, V of the raster (padded planes)
+  uint8_t * dst;               // row 0 (of plane 0 for CHW formats)
+  int64_t row_stride, plane_stride;   // bytes
+  uint32_t stride_y, stride_c; // padded widths of the luma and chroma planes
+  uint32_t width, height;      // display size
+  uint32_t groups;             // 16-pixel groups per row: (width + 15) / 16
+  uint32_t pad;
+};
+
 #define AA_MAX_XCD 16
 
 #define AA_SYNC_WS_DUMP 140
@@ -115,6 +126,9 @@ int launch_probe_concurrency( uint32_t * counter, uint32_t * seen, uint32_t n, u
 int launch_bind_rasters( const aa_raster_binding * b, int n, void * stream );
 // raster i (jobs[i]) -> staging + i * stride, one launch for the lot
 int launch_gather_rasters( const aa_gather_job * jobs, int n, uint8_t * staging, size_t stride, size_t max_bytes, void * stream );
+// jobs[i] -> RGB in `format` (AA_RGB_*), one launch for the lot; table: 3 x 256 output values (float formats); max_threads: the largest
+// job's groups * row pairs
+int launch_render_rgb( const aa_rgb_job * jobs, int n, int format, const uint32_t * table, uint32_t max_threads, void * stream );
 // per-window SSIM terms of two planes (stride = width; width a multiple of 8): (height/4 - 1) x (width/4 - 1) floats
 // dst = src with lf_level := byte `segment_id` of `levels` (records are 80 bytes, 16-byte aligned)
 int launch_lf_relevel( const aa_mb_info * src, aa_mb_info * dst, unsigned nmb, uint32_t levels, void * stream );

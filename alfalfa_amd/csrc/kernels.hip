@@ -1625,6 +1625,125 @@ __global__ __launch_bounds__( 256 ) void k_gather_rasters( const aa_gather_job *
   if ( blockIdx.x == 0 && threadIdx.x < ( J.bytes & 15 ) ) staging[stride * blockIdx.y + ( n16 << 4 ) + threadIdx.x] = J.src[( n16 << 4 ) + threadIdx.x];
 }
 
+// ---- Decoded frames to RGB (aa_render_rgb_async; the fragment shader of the reference's display, display.cc) ---------------
+// Integer form of the shader: chroma upsampled to 8x scale with the GL sampler's texel weights (co-sited horizontally, centred
+// vertically, clamp-to-edge inside the display chroma rectangle), SMPTE 170M limited-range matrix with 16 fractional bits, one
+// rounding at the end.  Float formats are a table lookup (3 x 256 entries, staged in LDS) of the u8 result.
+//
+// One thread = 16 adjacent pixels of a luma row pair: both rows share chroma row k = pair index and one neighbour row each, Y is two
+// 16-byte loads, each chroma row one 8-byte load plus the clamped ninth column.  Threads of one job run along the rows (row pairs
+// after each other), so a wave's stores cover whole lines.  A full group whose destination row is 16-byte aligned is written with
+// 16-byte stores; a partial group (the right edge) or an unaligned row takes a byte store path.  Nothing outside
+// [row start, row start + width * bytes per pixel) of a row (or plane) is written.
+constexpr int kRgbCy = 76309, kRgbCrv = 104574, kRgbCgu = 25642, kRgbCgv = 53281, kRgbCbu = 132213;
+
+// n elements of `esz` bytes (element values in the low bytes of e[]) at p: 16-byte stores when `fast`, else bytes
+template <int ESZ, int N>
+__device__ inline void rgb_store( uint8_t * p, const uint32_t ( &e )[N], const int n, const bool fast )
+{
+  static_assert( ( N * ESZ ) % 16 == 0, "whole 16-byte pieces" );
+  if ( fast ) {
+    uint32_t w[N * ESZ / 4];
+#pragma unroll
+    for ( int i = 0; i < N * ESZ / 4; i++ ) {
+      if ( ESZ == 1 ) w[i] = e[4 * i] | e[4 * i + 1] << 8 | e[4 * i + 2] << 16 | e[4 * i + 3] << 24;
+      else if ( ESZ == 2 ) w[i] = ( e[2 * i] & 0xFFFFu ) | e[2 * i + 1] << 16;
+      else w[i] = e[i];
+    }
+    uint4 * q = reinterpret_cast<uint4 *>( p );
+#pragma unroll
+    for ( int i = 0; i < N * ESZ / 16; i++ ) q[i] = make_uint4( w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3] );
+    return;
+  }
+#pragma unroll
+  for ( int i = 0; i < N; i++ )          // (unrolled: e[] stays in registers)
+    if ( i < n )
+#pragma unroll
+      for ( int b = 0; b < ESZ; b++ ) p[i * ESZ + b] = static_cast<uint8_t>( e[i] >> ( 8 * b ) );
+}
+
+template <int F>
+__global__ __launch_bounds__( 256 ) void k_render_rgb( const aa_rgb_job * jobs, const uint32_t * table )
+{
+  constexpr bool kFloat = F >= AA_RGB_F16_CHW;
+  constexpr int kEsz = F == AA_RGB_F32_CHW ? 4 : F >= AA_RGB_F16_CHW ? 2 : 1;
+  __shared__ uint32_t T[kFloat ? 768 : 1];
+  if ( kFloat ) {
+    for ( int i = threadIdx.x; i < 768; i += 256 ) T[i] = table[i];
+    __syncthreads();
+  }
+  const aa_rgb_job & J = jobs[blockIdx.y];
+  const uint32_t groups = J.groups, w = J.width, h = J.height;
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if ( t >= groups * ( ( h + 1 ) >> 1 ) ) return;
+  const int k = static_cast<int>( t / groups ), x0 = static_cast<int>( t - uint32_t( k ) * groups ) * 16;
+  const int cw = static_cast<int>( ( w + 1 ) >> 1 ), ch = static_cast<int>( ( h + 1 ) >> 1 );
+  const int j0 = x0 >> 1, je = min( j0 + 8, cw - 1 );
+  const int crow[3] = { max( k - 1, 0 ), k, min( k + 1, ch - 1 ) };
+  // chroma columns j0 .. j0 + 8 of rows k-1, k, k+1 (clamped), U then V
+  int c[2][3][9];
+#pragma unroll
+  for ( int p = 0; p < 2; p++ )
+#pragma unroll
+    for ( int r = 0; r < 3; r++ ) {
+      const uint8_t * row = J.plane[1 + p] + size_t( crow[r] ) * J.stride_c;
+      const uint2 q = *reinterpret_cast<const uint2 *>( row + j0 );
+      c[p][r][8] = row[je];
+#pragma unroll
+      for ( int i = 0; i < 8; i++ ) {
+        const int b = static_cast<int>( ( ( i < 4 ? q.x : q.y ) >> ( 8 * ( i & 3 ) ) ) & 255u );
+        c[p][r][i] = j0 + i > je ? c[p][r][8] : b;
+      }
+    }
+  const int n = min( 16, static_cast<int>( w ) - x0 );
+  for ( int r = 0; r < 2; r++ ) {
+    const int y = 2 * k + r;
+    if ( y >= static_cast<int>( h ) ) continue;
+    const uint4 yq = *reinterpret_cast<const uint4 *>( J.plane[0] + size_t( y ) * J.stride_y + x0 );
+    const uint32_t yw[4] = { yq.x, yq.y, yq.z, yq.w };
+    // 4x-scale vertical blends of both planes: row k weighted 3, the neighbour (above for even y, below for odd y) 1
+    int v[2][9];
+#pragma unroll
+    for ( int p = 0; p < 2; p++ )
+#pragma unroll
+      for ( int i = 0; i < 9; i++ ) v[p][i] = 3 * c[p][1][i] + c[p][r ? 2 : 0][i];
+    uint32_t R[16], G[16], B[16];
+#pragma unroll
+    for ( int i = 0; i < 16; i++ ) {
+      const int Y = static_cast<int>( ( yw[i >> 2] >> ( 8 * ( i & 3 ) ) ) & 255u );
+      const int j = i >> 1;
+      const int u8 = ( i & 1 ) ? v[0][j] + v[0][j + 1] : 2 * v[0][j];
+      const int v8 = ( i & 1 ) ? v[1][j] + v[1][j + 1] : 2 * v[1][j];
+      const int yt = 8 * kRgbCy * ( Y - 16 ), ut = u8 - 1024, vt = v8 - 1024;
+      R[i] = static_cast<uint32_t>( min( max( ( yt + kRgbCrv * vt + ( 1 << 18 ) ) >> 19, 0 ), 255 ) );
+      G[i] = static_cast<uint32_t>( min( max( ( yt - kRgbCgu * ut - kRgbCgv * vt + ( 1 << 18 ) ) >> 19, 0 ), 255 ) );
+      B[i] = static_cast<uint32_t>( min( max( ( yt + kRgbCbu * ut + ( 1 << 18 ) ) >> 19, 0 ), 255 ) );
+    }
+    uint8_t * const row = J.dst + y * J.row_stride;
+    if ( F == AA_RGB_U8_HWC3 || F == AA_RGB_U8_HWC4 ) {
+      constexpr int C = F == AA_RGB_U8_HWC3 ? 3 : 4;
+      uint32_t e[16 * C];
+#pragma unroll
+      for ( int i = 0; i < 16; i++ ) {
+        e[C * i] = R[i]; e[C * i + 1] = G[i]; e[C * i + 2] = B[i];
+        if ( C == 4 ) e[C * i + 3] = 255u;
+      }
+      uint8_t * const p = row + x0 * C;
+      rgb_store<1, 16 * C>( p, e, n * C, n == 16 && !( reinterpret_cast<uintptr_t>( p ) & 15 ) );
+    } else {
+#pragma unroll
+      for ( int ci = 0; ci < 3; ci++ ) {
+        const uint32_t * const src = ci == 0 ? R : ci == 1 ? G : B;
+        uint32_t e[16];
+#pragma unroll
+        for ( int i = 0; i < 16; i++ ) e[i] = kFloat ? T[ci * 256 + src[i]] : src[i];
+        uint8_t * const p = row + ci * J.plane_stride + x0 * kEsz;
+        rgb_store<kEsz, 16>( p, e, n, n == 16 && !( reinterpret_cast<uintptr_t>( p ) & 15 ) );
+      }
+    }
+  }
+}
+
 } // namespace
 
 // ---- SSIM windows of the encoder's loop-filter search (util/ssim.cc:57-71 -> libx264 pixel_ssim_wxh) -------
@@ -1690,6 +1809,26 @@ int launch_gather_rasters( const aa_gather_job * jobs, int n, uint8_t * staging,
   for ( int base = 0; base < n; base += 32768 ) {
     const int cnt = std::min( 32768, n - base );
     hipLaunchKernelGGL( k_gather_rasters, dim3( per, cnt ), dim3( 256 ), 0, static_cast<hipStream_t>( stream ), jobs + base, staging + stride * base, stride );
+    if ( hipError_t e = hipGetLastError() ) return static_cast<int>( e );
+  }
+  return 0;
+}
+
+int launch_render_rgb( const aa_rgb_job * jobs, int n, int format, const uint32_t * table, uint32_t max_threads, void * stream )
+{
+  const unsigned blocks = ( max_threads + 255u ) / 256u;
+  const hipStream_t st = static_cast<hipStream_t>( stream );
+  for ( int base = 0; base < n; base += 32768 ) {
+    const dim3 grid( blocks, std::min( 32768, n - base ) );
+    switch ( format ) {
+      case AA_RGB_U8_HWC3: hipLaunchKernelGGL( k_render_rgb<AA_RGB_U8_HWC3>, grid, dim3( 256 ), 0, st, jobs + base, table ); break;
+      case AA_RGB_U8_HWC4: hipLaunchKernelGGL( k_render_rgb<AA_RGB_U8_HWC4>, grid, dim3( 256 ), 0, st, jobs + base, table ); break;
+      case AA_RGB_U8_CHW: hipLaunchKernelGGL( k_render_rgb<AA_RGB_U8_CHW>, grid, dim3( 256 ), 0, st, jobs + base, table ); break;
+      case AA_RGB_F16_CHW: hipLaunchKernelGGL( k_render_rgb<AA_RGB_F16_CHW>, grid, dim3( 256 ), 0, st, jobs + base, table ); break;
+      case AA_RGB_BF16_CHW: hipLaunchKernelGGL( k_render_rgb<AA_RGB_BF16_CHW>, grid, dim3( 256 ), 0, st, jobs + base, table ); break;
+      case AA_RGB_F32_CHW: hipLaunchKernelGGL( k_render_rgb<AA_RGB_F32_CHW>, grid, dim3( 256 ), 0, st, jobs + base, table ); break;
+      default: return static_cast<int>( hipErrorInvalidValue );
+    }
     if ( hipError_t e = hipGetLastError() ) return static_cast<int>( e );
   }
   return 0;

@@ -212,6 +212,11 @@ static void ctx_free( aa_ctx * ctx )
   if ( ctx->last_raster_download ) (void) hipEventDestroy( ctx->last_raster_download );
   for ( auto & bb : ctx->bind_bufs ) { if ( bb.host ) (void) hipHostFree( bb.host ); if ( bb.done ) (void) hipEventDestroy( bb.done ); }
   for ( auto & gb : ctx->gather_bufs ) { if ( gb.host ) (void) hipHostFree( gb.host ); if ( gb.done ) (void) hipEventDestroy( gb.done ); if ( gb.copied ) (void) hipEventDestroy( gb.copied ); }
+  for ( auto & rb : ctx->rgb_bufs ) {
+    if ( rb.host ) (void) hipHostFree( rb.host );
+    if ( rb.dev ) (void) hipFree( rb.dev );
+    for ( hipEvent_t e : { rb.done, rb.before, rb.after } ) if ( e ) (void) hipEventDestroy( e );
+  }
   if ( ctx->ws ) (void) hipFree( ctx->ws );
   if ( ctx->boundary ) (void) hipFree( ctx->boundary );
   tok_free( ctx );

@@ -155,6 +155,103 @@ aa_status aa_stream_raster_device( aa_stream * s, int fi, void ** y, void ** u, 
   return AA_OK;
 }
 
+/* Shown frames as RGB in the caller's device memory (VideoDisplay::draw's shader, display.cc): one k_render_rgb launch on the compute
+ * stream for the lot, behind the decode of every frame it reads -- rasters are recycled in compute-stream order, so none can be
+ * written under it.  Job list and float table go through a ring of pinned buffers (like the gather lists of aa_download_batch_async). */
+aa_status aa_render_rgb_async( aa_ctx * ctx, aa_stream * const * streams, int n, const int * frame_index, int format,
+                               const aa_rgb_target * targets, const double mean[3], const double std[3], void * consumer_stream )
+{
+  if ( !ctx || !streams || !frame_index || !targets || n <= 0 ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: bad argument" );
+  if ( format < AA_RGB_U8_HWC3 || format > AA_RGB_F32_CHW ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: unknown format " + std::to_string( format ) );
+  const bool is_float = format >= AA_RGB_F16_CHW, chw = format >= AA_RGB_U8_CHW;
+  if ( !is_float && ( mean || std ) ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: mean / std apply to the float formats only" );
+  if ( std ) for ( int c = 0; c < 3; c++ ) if ( std[c] == 0 ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: std[" + std::to_string( c ) + "] is 0" );
+  if ( aa_status st = set_device( ctx ) ) return st;
+  static const int kPixelBytes[6] = { 3, 4, 1, 2, 2, 4 };
+  const int64_t bpp = kPixelBytes[format];
+  uint64_t max_threads = 0;
+  for ( int i = 0; i < n; i++ ) {
+    const aa_stream * s = streams[i];
+    if ( !s || s->ctx != ctx ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: stream belongs to another context" );
+    const int fi = frame_index[i];
+    if ( fi < 0 || fi >= static_cast<int>( s->frames.size() ) ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: bad frame index" );
+    const FrameRec & r = s->frames[fi];
+    if ( !r.handle_held ) return fail( AA_ERR_LOGIC, "aa_render_rgb_async: frame was released" );
+    if ( fi >= s->next_submit || !r.placed ) return fail( AA_ERR_LOGIC, "aa_render_rgb_async: frame not decoded yet" );
+    const aa_rgb_target & t = targets[i];
+    const int64_t w = s->parser.width(), h = s->parser.height();
+    if ( !t.dst ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: null dst" );
+    if ( t.row_stride < w * bpp ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: row stride smaller than a row" );
+    if ( chw && t.plane_stride < h * t.row_stride ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: plane stride smaller than height * row stride" );
+    max_threads = std::max<uint64_t>( max_threads, uint64_t( ( w + 15 ) / 16 ) * uint64_t( ( h + 1 ) / 2 ) );
+  }
+  constexpr size_t kTableBytes = 768 * sizeof( uint32_t );
+  const int bi = ctx->next_rgb_buf;
+  aa_ctx::RgbBuf & rb = ctx->rgb_bufs[bi];
+  ctx->next_rgb_buf = ( ctx->next_rgb_buf + 1 ) % aa_ctx::kBindBufs;
+  if ( rb.busy ) { HIP_TRY( hipEventSynchronize( rb.done ) ); rb.busy = false; }
+  const size_t bytes = kTableBytes + size_t( n ) * sizeof( aa_rgb_job );
+  if ( rb.cap < bytes ) {
+    if ( rb.dev ) HIP_TRY( hipStreamSynchronize( ctx->compute ) );      // (a render queued 16 calls ago may still read it)
+    if ( rb.host ) (void) hipHostFree( rb.host );
+    if ( rb.dev ) (void) hipFree( rb.dev );
+    rb.host = rb.dev = nullptr; rb.cap = 0;
+    const size_t cap = kTableBytes + std::max<size_t>( 512, size_t( n ) * 2 ) * sizeof( aa_rgb_job );
+    HIP_TRY( hipHostMalloc( reinterpret_cast<void **>( &rb.host ), cap, hipHostMallocDefault ) );
+    HIP_TRY( hipMalloc( reinterpret_cast<void **>( &rb.dev ), cap ) );
+    rb.cap = cap;
+  }
+  for ( hipEvent_t * e : { &rb.done, &rb.before, &rb.after } ) if ( !*e ) HIP_TRY( hipEventCreateWithFlags( e, hipEventDisableTiming ) );
+  // float formats: out = T_c[rgb], T_c[i] = (i / 255 - mean_c) / std_c in double, rounded to float, then to half / bfloat16 (nearest even)
+  uint32_t * table = reinterpret_cast<uint32_t *>( rb.host );
+  if ( is_float )
+    for ( int c = 0; c < 3; c++ )
+      for ( int i = 0; i < 256; i++ ) {
+        const float f = static_cast<float>( ( i / 255.0 - ( mean ? mean[c] : 0.0 ) ) / ( std ? std[c] : 1.0 ) );
+        uint32_t bits;
+        std::memcpy( &bits, &f, 4 );
+        if ( format == AA_RGB_F16_CHW ) {
+          const _Float16 hf = static_cast<_Float16>( f );
+          uint16_t hb;
+          std::memcpy( &hb, &hf, 2 );
+          bits = hb;
+        } else if ( format == AA_RGB_BF16_CHW ) {
+          bits = ( bits & 0x7FFFFFFFu ) > 0x7F800000u ? ( bits >> 16 ) | 0x40u : ( bits + 0x7FFFu + ( ( bits >> 16 ) & 1u ) ) >> 16;
+        }
+        table[c * 256 + i] = bits;
+      }
+  aa_rgb_job * jobs = reinterpret_cast<aa_rgb_job *>( rb.host + kTableBytes );
+  for ( int i = 0; i < n; i++ ) {
+    aa_stream * s = streams[i];
+    const int slot = s->frames[frame_index[i]].out_slot;
+    aa_rgb_job & j = jobs[i];
+    for ( int p = 0; p < 3; p++ ) j.plane[p] = slot_plane( s, slot, p );
+    j.dst = static_cast<uint8_t *>( targets[i].dst );
+    j.row_stride = targets[i].row_stride;
+    j.plane_stride = chw ? targets[i].plane_stride : 0;
+    j.stride_y = s->pw; j.stride_c = s->pw / 2;
+    j.width = s->parser.width(); j.height = s->parser.height();
+    j.groups = ( j.width + 15 ) / 16;
+    j.pad = 0;
+  }
+  const hipStream_t consumer = static_cast<hipStream_t>( consumer_stream );
+  if ( consumer ) {
+    HIP_TRY( hipEventRecord( rb.before, consumer ) );
+    HIP_TRY( hipStreamWaitEvent( ctx->compute, rb.before, 0 ) );
+  }
+  HIP_TRY( hipMemcpyAsync( rb.dev, rb.host, bytes, hipMemcpyHostToDevice, ctx->compute ) );
+  HIP_TRY( hipEventRecord( rb.done, ctx->compute ) );
+  rb.busy = true;
+  if ( int e = aa::launch_render_rgb( reinterpret_cast<const aa_rgb_job *>( rb.dev + kTableBytes ), n, format, reinterpret_cast<const uint32_t *>( rb.dev ),
+                                      static_cast<uint32_t>( max_threads ), ctx->compute ) )
+    return hip_fail( static_cast<hipError_t>( e ), "k_render_rgb" );
+  if ( consumer ) {
+    HIP_TRY( hipEventRecord( rb.after, ctx->compute ) );
+    HIP_TRY( hipStreamWaitEvent( consumer, rb.after, 0 ) );
+  }
+  return AA_OK;
+}
+
 aa_status aa_stream_references( const aa_stream * s, int * last, int * golden, int * alternate )
 {
   if ( !s ) return fail( AA_ERR_ARGUMENT, "null stream" );

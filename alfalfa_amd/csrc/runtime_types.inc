@@ -175,6 +175,11 @@ struct aa_ctx {
   struct GatherBuf { aa_gather_job * host = nullptr, * dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr, copied = nullptr; bool busy = false; };
   GatherBuf gather_bufs[kBindBufs];
   int next_gather_buf = 0;
+  // the job list and float table of a render (aa_render_rgb_async): written to `host` (pinned), copied to `dev` on the compute stream
+  // ahead of k_render_rgb; `done` fires when the copy has read `host`.  before / after: the waits on the caller's stream
+  struct RgbBuf { uint8_t * host = nullptr, * dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr, before = nullptr, after = nullptr; bool busy = false; };
+  RgbBuf rgb_bufs[kBindBufs];
+  int next_rgb_buf = 0;
   int row_handoff_by_kernel[2] = { 0, 0 };   // (diagnostics: waits the second look ended, k_recon_intra4 / k_loopfilter_rows4)
   std::deque<int> downloads_in_flight;   // gather_bufs whose copy (aa_download_batch_async) nobody has waited for yet, oldest first
   // A parse batch holds its stream for as long as its longest chain (seconds for a key frame): a batch queued behind another

@@ -205,6 +205,75 @@ class Context:
         else:
             capi.check(self.L.aa_ctx_download_wait_until(self.h, int(max_in_flight)))
 
+    # format -> (AA_RGB_* code, torch dtype, channels of an HWC format / None for CHW)
+    RGB_FORMATS = {"rgb24": (capi.AA_RGB_U8_HWC3, "uint8", 3), "rgba": (capi.AA_RGB_U8_HWC4, "uint8", 4),
+                   "chw_u8": (capi.AA_RGB_U8_CHW, "uint8", None), "chw_f16": (capi.AA_RGB_F16_CHW, "float16", None),
+                   "chw_bf16": (capi.AA_RGB_BF16_CHW, "bfloat16", None), "chw_f32": (capi.AA_RGB_F32_CHW, "float32", None)}
+
+    def to_rgb(self, decoders, frame_indices, format="rgb24", mean=None, std=None, out=None):
+        """Frame frame_indices[i] of decoders[i] as RGB on this context's device, all in one kernel (aa_render_rgb_async): the
+        display rectangle, SMPTE 170M limited range, as the reference's display shader shows it.
+        -> torch tensor (N, H, W, 3|4) uint8 for "rgb24" / "rgba", (N, 3, H, W) for "chw_u8" / "chw_f16" / "chw_bf16" / "chw_f32"
+        (float formats: (rgb / 255 - mean[c]) / std[c]).  The result is ordered on torch.cuda.current_stream(): torch ops may use it
+        without a sync.  out: a tensor of that shape, or a list of per-frame tensors ((H, W, C) / (3, H, W); frames of different
+        display sizes need this form); views with padded rows are accepted, the innermost dimension must be contiguous."""
+        import torch
+        if format not in self.RGB_FORMATS:
+            raise ValueError("unknown RGB format %r (one of %s)" % (format, ", ".join(self.RGB_FORMATS)))
+        code, dtype_name, hwc = self.RGB_FORMATS[format]
+        dtype = getattr(torch, dtype_name)
+        n = len(decoders)
+        if n == 0 or len(frame_indices) != n:
+            raise ValueError("to_rgb: need as many frame indices as decoders, and at least one")
+        device = torch.device("cuda", self.device)
+
+        def frame_shape(d):
+            return (d.height, d.width, hwc) if hwc else (3, d.height, d.width)
+
+        if isinstance(out, (list, tuple)):
+            if len(out) != n:
+                raise ValueError("to_rgb: out has %d tensors for %d frames" % (len(out), n))
+            frames = result = list(out)
+        else:
+            shapes = {frame_shape(d) for d in decoders}
+            if len(shapes) != 1:
+                raise ValueError("to_rgb: frames of different display sizes need out= as a list of tensors")
+            shape = (n,) + shapes.pop()
+            if out is None:
+                out = torch.empty(shape, dtype=dtype, device=device)
+            elif tuple(out.shape) != shape:
+                raise ValueError("to_rgb: out has shape %s, expected %s" % (tuple(out.shape), shape))
+            result, frames = out, list(out.unbind(0))
+        targets = (capi.RgbTarget * n)()
+        for i, (t, d) in enumerate(zip(frames, decoders)):
+            if tuple(t.shape) != frame_shape(d):
+                raise ValueError("to_rgb: out[%d] has shape %s, expected %s" % (i, tuple(t.shape), frame_shape(d)))
+            if t.dtype != dtype or t.device != device:
+                raise ValueError("to_rgb: out[%d] is %s on %s, expected %s on %s" % (i, t.dtype, t.device, dtype, device))
+            es = t.element_size()
+            if hwc and (t.stride(2) != 1 or t.stride(1) != hwc):
+                raise ValueError("to_rgb: out[%d]: the pixels of a row must be contiguous" % i)
+            if not hwc and t.stride(2) != 1:
+                raise ValueError("to_rgb: out[%d]: the rows must be contiguous" % i)
+            targets[i].dst = t.data_ptr()
+            targets[i].row_stride = t.stride(0 if hwc else 1) * es
+            targets[i].plane_stride = 0 if hwc else t.stride(0) * es
+        arr = (C.c_void_p * n)(*[d.h for d in decoders])
+        idx = (C.c_int * n)(*frame_indices)
+        m = None if mean is None else (C.c_double * 3)(*[float(x) for x in mean])
+        sd = None if std is None else (C.c_double * 3)(*[float(x) for x in std])
+        cur = torch.cuda.current_stream(device)
+        compute = None
+        if not cur.cuda_stream:
+            # torch's default stream is HIP's null stream, whose handle (0) means "no consumer stream" to the C call: the same two
+            # waits are made through torch's own events instead
+            compute = torch.cuda.ExternalStream(self.compute_stream(), device=device)
+            compute.wait_stream(cur)
+        capi.check(self.L.aa_render_rgb_async(self.h, arr, n, idx, code, targets, m, sd, C.c_void_p(cur.cuda_stream or None)))
+        if compute is not None:
+            cur.wait_stream(compute)
+        return result
+
     def decode_batch(self, decoders, frame_indices):
         n = len(decoders)
         arr = (C.c_void_p * n)(*[d.h for d in decoders])
@@ -360,6 +429,10 @@ class Decoder:
         y, u, v = self.raster(frame_index)
         w, h = self.width, self.height
         return y[:h, :w].tobytes() + u[:(h + 1) // 2, :(w + 1) // 2].tobytes() + v[:(h + 1) // 2, :(w + 1) // 2].tobytes()
+
+    def rgb(self, frame_index, format="rgb24", mean=None, std=None, out=None):
+        """One frame as RGB on the device (Context.to_rgb): (H, W, 3|4) or (3, H, W); out: a tensor of that shape."""
+        return self.ctx.to_rgb([self], [frame_index], format, mean, std, None if out is None else [out])[0]
 
     def raster_device_pointers(self, frame_index):
         y, u, v = C.c_void_p(), C.c_void_p(), C.c_void_p()

@@ -351,6 +351,22 @@ aa_status aa_ctx_download_wait( aa_ctx * ctx );
 aa_status aa_ctx_download_wait_until( aa_ctx * ctx, int max_in_flight );
 /* Device pointers of a frame's planes (valid while the frame's raster is alive). */
 aa_status aa_stream_raster_device( aa_stream * s, int frame_index, void ** y, void ** u, void ** v );
+/* Decoded frames to RGB on the device (what the reference's display shader does with every shown raster, display.cc): frame
+ * frame_index[i] of streams[i] -> targets[i], the display rectangle (height rows of width pixels), all n in ONE kernel on the
+ * compute stream behind the decode of those frames.  SMPTE 170M (BT.601) limited range; chroma co-sited horizontally, centred
+ * vertically, bilinear with clamp-to-edge; exact integer definition in INTEGRATION.md.
+ *   AA_RGB_U8_HWC3 / AA_RGB_U8_HWC4: rows of packed R G B (A = 255) bytes;  AA_RGB_*_CHW: three planes R, G, B of height rows
+ *   targets[i].dst = first byte of row 0 (of plane R); row_stride >= width * bytes per pixel; plane_stride (CHW only) >= height *
+ *   row_stride; nothing outside [row start, row start + width * bytes per pixel) of a row is written
+ *   mean / std (float formats only; NULL = 0 / 1): out = (rgb / 255 - mean[c]) / std[c], computed in double, rounded to float and
+ *   then to the output type (round to nearest even)
+ * consumer_stream (a hipStream_t): the compute stream waits for it before the kernel (dst may have just been allocated there), and it
+ * waits for the kernel.  NULL: no consumer stream, dst is valid after aa_ctx_sync (a consumer on HIP's null stream makes the two
+ * waits itself, with events on aa_ctx_compute_stream). */
+enum { AA_RGB_U8_HWC3 = 0, AA_RGB_U8_HWC4 = 1, AA_RGB_U8_CHW = 2, AA_RGB_F16_CHW = 3, AA_RGB_BF16_CHW = 4, AA_RGB_F32_CHW = 5 };
+typedef struct aa_rgb_target { void * dst; int64_t row_stride; int64_t plane_stride; } aa_rgb_target;  /* bytes; plane_stride: CHW only */
+aa_status aa_render_rgb_async( aa_ctx * ctx, aa_stream * const * streams, int n, const int * frame_index, int format,
+                               const aa_rgb_target * targets, const double mean[3], const double std[3], void * consumer_stream );
 /* References::last/golden/alternative after the most recently SUBMITTED frame: frame indices (-1 = initial blank). */
 aa_status aa_stream_references( const aa_stream * s, int * last, int * golden, int * alternate );
 /* Identity of the three reference rasters as they stand now (all frames handed to aa_decode_batch so far applied): equal

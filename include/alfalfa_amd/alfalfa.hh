@@ -384,6 +384,25 @@ public:
   bool operator!=( const RasterHandle & o ) const { return !operator==( o ); }
 };
 
+// Extension beside the reference's names (what VideoDisplay::draw's shader does with a shown raster, display.cc): decoded rasters
+// -> RGB in the caller's device buffers, one kernel for the lot (aa_render_rgb_async: formats AA_RGB_*, targets in bytes).  Every
+// raster must come from a decoded frame of a decoder on one context.  With consumer_stream null (a hipStream_t otherwise, which is
+// then ordered behind the kernel), the buffers are valid after that context's sync().
+inline void render_rgb( const std::vector<RasterHandle> & rasters, const std::vector<aa_rgb_target> & targets, const int format = AA_RGB_U8_HWC3,
+                        void * const consumer_stream = nullptr )
+{
+  if ( rasters.empty() || rasters.size() != targets.size() ) throw LogicError();
+  std::vector<aa_stream *> streams;
+  std::vector<int> frames;
+  for ( const RasterHandle & r : rasters ) {
+    if ( r.frame_index() < 0 || r.owner()->ctx != rasters.front().owner()->ctx ) throw LogicError();
+    streams.push_back( r.owner()->stream );
+    frames.push_back( r.frame_index() );
+  }
+  check( aa_render_rgb_async( rasters.front().owner()->ctx->get(), streams.data(), static_cast<int>( streams.size() ), frames.data(), format,
+                              targets.data(), nullptr, nullptr, consumer_stream ) );
+}
+
 enum reference_frame { CURRENT_FRAME, LAST_FRAME, GOLDEN_FRAME, ALTREF_FRAME };     // modemv_data.hh
 
 struct References
