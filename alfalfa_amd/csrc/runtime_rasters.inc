@@ -95,7 +95,11 @@ aa_status aa_download_batch_async( aa_ctx * ctx, aa_stream * const * streams, in
   aa_ctx::GatherBuf & gb = ctx->gather_bufs[gi];
   ctx->next_gather_buf = ( ctx->next_gather_buf + 1 ) % aa_ctx::kBindBufs;
   if ( gb.busy ) { HIP_TRY( hipEventSynchronize( gb.done ) ); gb.busy = false; }
-  // (the buffer comes round again: whoever still counted its previous copy as in flight sees it finished -- kBindBufs copies later it is)
+  // The buffer comes round again.  If its previous download is still on the list (more than kBindBufs queued and nobody waited for
+  // it), its copy may still be writing the caller's memory, and gb.copied -- the only handle on it -- is recorded anew below: the copy
+  // is waited for HERE, before the index leaves the list, so that aa_ctx_download_wait_until never counts a running copy as arrived.
+  if ( gb.copied && std::find( ctx->downloads_in_flight.begin(), ctx->downloads_in_flight.end(), gi ) != ctx->downloads_in_flight.end() )
+    HIP_TRY( hipEventSynchronize( gb.copied ) );
   for ( auto it = ctx->downloads_in_flight.begin(); it != ctx->downloads_in_flight.end(); ) it = *it == gi ? ctx->downloads_in_flight.erase( it ) : it + 1;
   if ( gb.cap < static_cast<size_t>( n ) ) {
     if ( gb.host ) (void) hipHostFree( gb.host );
