@@ -545,27 +545,14 @@ constexpr int kMinPolls = 1 << 24;
 // (buffer_inv sc1), the address per lane (a vector-addressed load, not the scalar-base form of the poll), system scope, and a
 // read-modify-write that the L2 itself executes.  progress only grows, so the larger value is the truth.  Counted (ws->dump[RESCUES..]):
 // how many waits ended this way, and by which read.
-#ifndef AA_HANDOFF_PUBLISH_AGENT
-#define AA_HANDOFF_PUBLISH_AGENT 0    /* build parameter (A/B runs): 1 = a row's progress word is stored with agent scope (sc1: written through), not workgroup scope */
-#endif
-#if AA_HANDOFF_PUBLISH_AGENT
-#define AA_PUBLISH_SCOPE __HIP_MEMORY_SCOPE_AGENT
-#else
-#define AA_PUBLISH_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
-#endif
-#ifndef AA_HANDOFF_POLL_FORM
-#define AA_HANDOFF_POLL_FORM 0        /* build parameter (A/B runs): 1 = the poll itself is a vector-addressed load */
-#endif
-#ifndef AA_HANDOFF_LOOK_EVERY
-#define AA_HANDOFF_LOOK_EVERY 1024    /* build parameter (A/B runs): polls between two second looks (a power of two) */
-#endif
+constexpr int kLookEvery = 1024;      // polls between two second looks (a power of two)
+// The scope a row's progress word is stored with.  Workgroup: the store lands in the L2 of the XCD the whole unit runs on, which is where
+// the row below polls it.  Agent scope (sc1: written through) is what the memory model asks for between two workgroups
+// -- the conformant alternative.  Measured, session 21: it costs the row kernels 10-14 % alone (k_loopfilter_rows4 2.55 -> 2.91 ms,
+// k_recon_intra4 1.07 -> 1.18), end to end within the spread.
+constexpr int kPublishScope = __HIP_MEMORY_SCOPE_WORKGROUP;
 __device__ __forceinline__ int poll_progress( const int * p )
 {
-#if AA_HANDOFF_POLL_FORM
-  int off = 0;
-  asm volatile( "" : "+v"( off ) );
-  p += off;
-#endif
   return __hip_atomic_load( p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
 }
 __device__ __forceinline__ int reread_progress( aa_sync_ws * ws, const int * p, const int seen, const int need, const int kernel )
@@ -605,13 +592,47 @@ __device__ __noinline__ void wait_expired( aa_sync_ws * ws, const int code, cons
     ws->dump[128] = spins; ws->dump[129] = static_cast<int>( waited / 100000ull ); ws->dump[130] = mbh;      // (ms)
   }
 }
+__device__ __forceinline__ int xcc_id() { return static_cast<int>( __builtin_amdgcn_s_getreg( 20 | ( 0 << 6 ) | ( 3 << 11 ) ) ); }   // HW_REG_XCC_ID[3:0]
+// Publish: everything this wave has stored so far has reached the L2 (the drain), then `cols` columns of the row are final.  All lanes
+// drain; the lanes of `who` store the word.
+__device__ __forceinline__ void publish_progress( const bool who, int * word, const int cols )
+{
+  asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
+  if ( who ) __hip_atomic_store( word, cols, __ATOMIC_RELAXED, kPublishScope );
+}
+
+// Wait until every lane that is `on` has seen `need` columns of the row above (seen: what it knows so far, in and out).  Gives up -- and
+// leaves why in ws -- when another wave has reported an error, when the wave finds itself off its home XCD, or when the wait has outlasted
+// both bounds (see above).  kernel: 1 = k_recon_intra4, 2 = k_loopfilter_rows4 (the error code of an expired wait and the rescue counter).
+// Argument order: who waits for what (on, need, seen), who says so if it fails (kernel, ws), where (progress = the unit's row words, group,
+// row, mbh = rows the dump covers, home_xcc), how long (min_polls AND max_wait_ticks must both be exceeded).
+__device__ __forceinline__ void wait_for_row_above( const bool on, const int need, int & seen, const int kernel, aa_sync_ws * ws, const int * progress, const int group,
+                                                    const int row, const int mbh, const int home_xcc, const int min_polls, const unsigned long long max_wait_ticks )
+{
+  int spins = 0;
+  unsigned long long wait_t0 = 0;
+  while ( !__all( !on || seen >= need ) ) {
+    __builtin_amdgcn_s_sleep( 4 );
+    if ( on && seen < need ) seen = poll_progress( &progress[row - 1] );
+    ++spins;
+    if ( ( spins & ( kLookEvery - 1 ) ) == 0 && on ) seen = reread_progress( ws, &progress[row - 1], seen, need, kernel );
+    if ( ( spins & 1023 ) == 0 ) {
+      if ( __hip_atomic_load( &ws->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ) ) break;
+      // the hand-off is only coherent inside the XCD the ticket was taken on: a wave that finds itself on another one (context save /
+      // restore under queue oversubscription) says so instead of waiting for the watchdog
+      if ( xcc_id() != home_xcc ) { if ( threadIdx.x == 0 && atomicCAS( &ws->error, 0, 4 ) == 0 ) { ws->where[0] = group; ws->where[1] = row; ws->where[2] = ( home_xcc << 16 ) | xcc_id(); } break; }
+      const unsigned long long now = wall_clock64();
+      if ( !wait_t0 ) wait_t0 = now;
+      else if ( spins > min_polls && now - wait_t0 > max_wait_ticks ) { wait_expired( ws, kernel, group, row, need, seen, progress, mbh, spins, now - wait_t0 ); break; }
+    }
+  }
+}
 // Test hooks riding in k_loopfilter_rows4's `dbg` argument (ALFALFA_AMD_LF_DEBUG, see lf_debug_bits): bit 5 = FAULT INJECTION -- row 1 of every
 // unit never publishes its progress, so row 2 waits until its wait expires (tests/test_gpu_parity.py: the error, its dump and that nothing
 // hangs); bits 8-15 = the wait's time bound in quarters of a second (0: kMaxWaitTicks), bits 16-20 = log2 of its poll bound (0: kMinPolls).
 __device__ __forceinline__ bool lf_fault_injected( const int dbg, const int row ) { return ( dbg & 32 ) && row == 1; }
 __device__ __forceinline__ unsigned long long lf_max_wait_ticks( const int dbg ) { const int q = ( dbg >> 8 ) & 255; return q ? static_cast<unsigned long long>( q ) * 25000000ull : kMaxWaitTicks; }
 __device__ __forceinline__ int lf_min_polls( const int dbg ) { const int e = ( dbg >> 16 ) & 31; return e ? 1 << e : kMinPolls; }
-__device__ __forceinline__ int xcc_id() { return static_cast<int>( __builtin_amdgcn_s_getreg( 20 | ( 0 << 6 ) | ( 3 << 11 ) ) ); }   // HW_REG_XCC_ID[3:0]
 
 __device__ __forceinline__ int take_ticket( aa_sync_ws * ws, const int xcc, int * slot, const int lane )
 {
@@ -873,8 +894,7 @@ __device__ __forceinline__ void recon_intra4_row( const aa_frame_list & list, co
     // everything left of `col` in this row is final: the previous macroblock's stores have reached the L2.  A slot that
     // has run out of intra macroblocks publishes the whole row at once -- it must not hold the rows below it back until
     // the OTHER three frames of the wave are through.
-    asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
-    if ( frame_on && l == 0 && ( on || !row_done ) ) __hip_atomic_store( &progress[row], on ? col : mbw, __ATOMIC_RELAXED, AA_PUBLISH_SCOPE );
+    publish_progress( frame_on && l == 0 && ( on || !row_done ), &progress[row], on ? col : mbw );
     row_done = row_done || !on;
 
     const aa_mb_info * const mb = f.mbs + static_cast<size_t>( row ) * mbw + col;
@@ -891,25 +911,7 @@ __device__ __forceinline__ void recon_intra4_row( const aa_frame_list & list, co
     residual_x4( S, f, has_res, has_y2, nz_mask, coeff_index, hd.y >> 24, segment, l );
 
     // ---- wait for the row above, then stage the neighbours (sc1 loads: L1-bypassing, served by this XCD's L2) ----
-    if ( row > 0 ) {
-      int spins = 0;
-      unsigned long long wait_t0 = 0;
-      while ( !__all( !on || seen >= need ) ) {
-        __builtin_amdgcn_s_sleep( 4 );
-        if ( on && seen < need ) seen = poll_progress( &progress[row - 1] );
-        ++spins;
-        if ( ( spins & ( AA_HANDOFF_LOOK_EVERY - 1 ) ) == 0 && on ) seen = reread_progress( ws, &progress[row - 1], seen, need, 1 );
-        if ( ( spins & 1023 ) == 0 ) {
-          if ( __hip_atomic_load( &ws->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ) ) break;
-          // the hand-off is only coherent inside the XCD the ticket was taken on: a wave that finds itself elsewhere says so
-          if ( xcc_id() != home_xcc ) { if ( lane == 0 && atomicCAS( &ws->error, 0, 4 ) == 0 ) { ws->where[0] = group; ws->where[1] = row; ws->where[2] = ( home_xcc << 16 ) | xcc_id(); } break; }
-          const unsigned long long now = wall_clock64();
-          if ( !wait_t0 ) wait_t0 = now;
-          else if ( spins > kMinPolls && now - wait_t0 > kMaxWaitTicks ) { wait_expired( ws, 1, group, row, need, seen, progress, mbh_max, spins, now - wait_t0 ); break; }
-        }
-      }
-
-    }
+    if ( row > 0 ) wait_for_row_above( on, need, seen, 1, ws, progress, group, row, mbh_max, home_xcc, kMinPolls, kMaxWaitTicks );
     const int x0 = col * 16, cx0 = col * 8;
     if ( on ) {
       if ( l < 6 ) {               // the row above, cols -4..19 as six dwords (prediction.cc:99-167 edge rules)
@@ -998,8 +1000,7 @@ __device__ __forceinline__ void recon_intra4_row( const aa_frame_list & list, co
     }
     __syncthreads();
   }
-  asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
-  if ( frame_on && l == 0 && !row_done ) __hip_atomic_store( &progress[row], mbw, __ATOMIC_RELAXED, AA_PUBLISH_SCOPE );
+  publish_progress( frame_on && l == 0 && !row_done, &progress[row], mbw );
 }
 
 __global__ __launch_bounds__( kLanes ) void k_recon_intra4( const aa_frame_list list, const int n_groups, const int mbh_max, aa_sync_ws * ws, const int n_xcd )
@@ -1281,10 +1282,7 @@ __global__ __launch_bounds__( kLanes ) void k_recon_inter4( const aa_frame_list 
 //     macroblock, to a BOUNDARY buffer; the workgroup of the next macroblock row reads that line as its rows -4..-1,
 //     finishes them with its top MB edge and stores them with its own strip.  Frame rows are therefore written by
 //     exactly one workgroup and cross-row hand-off costs one line per macroblock each way (+ a 4-byte-column fix-up).
-#ifndef AA_LF_STRIP_MBS
-#define AA_LF_STRIP_MBS 8
-#endif
-constexpr int kStripMbs = AA_LF_STRIP_MBS;                         // 8: whole 128-byte lines, 19 KB of LDS per wave (2 waves per SIMD); 4: half lines, 11 KB, 3 waves per SIMD -- measured: same speed, 1.35x the HBM traffic
+constexpr int kStripMbs = 8;                          // 8: whole 128-byte lines, 19 KB of LDS per wave (2 waves per SIMD); 4: half lines, 11 KB, 3 waves per SIMD -- measured: same speed, 1.35x the HBM traffic
 constexpr int kStripRow = 16 + 16 * kStripMbs;        // LDS row: 16 bytes of padding + the strip's luma columns (U | V halves for chroma rows)
 constexpr int kStripRpi = 16 / kStripMbs;             // pixel rows covered by one bulk load/store instruction (16 lanes = chunks x rows)
 static_assert( ( kStripRow / 16 ) % 2 == 1, "odd multiple of 16: consecutive rows start on different banks" );
@@ -1453,24 +1451,8 @@ __device__ __forceinline__ void loopfilter_strip_row( const aa_frame_list & list
       }
 
       if ( row > 0 ) {
-        int spins = 0;
-        unsigned long long wait_t0 = 0;
-        while ( !__all( seen >= need ) && !( dbg & 16 ) ) {
-          __builtin_amdgcn_s_sleep( 4 );
-          if ( seen < need ) seen = poll_progress( &progress[row - 1] );
-          ++spins;
-          if ( ( spins & ( AA_HANDOFF_LOOK_EVERY - 1 ) ) == 0 ) seen = reread_progress( ws, &progress[row - 1], seen, need, 2 );
-          if ( ( spins & 1023 ) == 0 ) {
-            if ( __hip_atomic_load( &ws->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ) ) break;
-            // the hand-off is only coherent inside one XCD: a wave that finds itself on another one (context save / restore
-            // under queue oversubscription) says so instead of waiting for the watchdog
-            if ( xcc_id() != home_xcc ) { if ( lane == 0 && atomicCAS( &ws->error, 0, 4 ) == 0 ) { ws->where[0] = group; ws->where[1] = row; ws->where[2] = ( home_xcc << 16 ) | xcc_id(); } break; }
-            const unsigned long long now = wall_clock64();
-            if ( !wait_t0 ) wait_t0 = now;
-            else if ( spins > lf_min_polls( dbg ) && now - wait_t0 > lf_max_wait_ticks( dbg ) ) { wait_expired( ws, 2, group, row, need, seen, progress, mbh, spins, now - wait_t0 ); break; }
-          }
-        }
-  
+        if ( !( dbg & 16 ) ) wait_for_row_above( true, need, seen, 2, ws, progress, group, row, mbh, home_xcc, lf_min_polls( dbg ), lf_max_wait_ticks( dbg ) );
+
         // rows -4..-1: the boundary line the row above left for this macroblock (sc1: bypass L1, served by the XCD's L2)
         if ( frame_on && l < 8 && !( dbg & 8 ) ) {
           const uint8_t * src = bnd_top + static_cast<size_t>( col ) * 128;
@@ -1482,8 +1464,7 @@ __device__ __forceinline__ void loopfilter_strip_row( const aa_frame_list & list
       }
       // every boundary line up to macroblock col-1 is complete and has reached the L2 (the fix-up above drained behind the
       // wait for the row above): publish
-      asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
-      if ( lane == 0 && col > 0 && !lf_fault_injected( dbg, row ) ) __hip_atomic_store( &progress[row], col, __ATOMIC_RELAXED, AA_PUBLISH_SCOPE );
+      publish_progress( lane == 0 && col > 0 && !lf_fault_injected( dbg, row ), &progress[row], col );
       // the next strip's own rows: issued here so that no wait of THIS step covers them (vmcnt completes in order); they
       // have the rest of the strip to arrive
       if ( k == 0 && s + 1 < n_strips ) prefetch( s + 1 );
@@ -1542,8 +1523,7 @@ __device__ __forceinline__ void loopfilter_strip_row( const aa_frame_list & list
       __syncthreads();
     }
   }
-  asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );       // the last macroblock's line has no right neighbour to wait for
-  if ( lane == 0 && !lf_fault_injected( dbg, row ) ) __hip_atomic_store( &progress[row], mbw, __ATOMIC_RELAXED, AA_PUBLISH_SCOPE );
+  publish_progress( lane == 0 && !lf_fault_injected( dbg, row ), &progress[row], mbw );       // the last macroblock's line has no right neighbour to wait for
 }
 
 __device__ __forceinline__ void loopfilter_rows4_body( const aa_frame_list & list, const int n_groups, const int mbh_max, const int mbw_max, aa_sync_ws * ws, uint8_t * bnd,

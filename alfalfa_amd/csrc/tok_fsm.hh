@@ -64,22 +64,6 @@
 
 #include "parse_common.hh"
 
-#ifndef AA_STEP_UNROLL
-#define AA_STEP_UNROLL 1              /* build parameter (A/B runs): the kBendEvery steps of a group unrolled */
-#endif
-#ifndef AA_STEP_SCHED_BARRIER
-#define AA_STEP_SCHED_BARRIER 1       /* build parameter (A/B runs): a scheduling barrier between the load-independent and the load-dependent half of a step */
-#endif
-#ifndef AA_SLICE_SKEW
-#define AA_SLICE_SKEW 0               /* build parameter (A/B runs) */
-#endif
-#ifndef AA_STEP_STORE_ALWAYS
-#define AA_STEP_STORE_ALWAYS 2        /* build parameter (A/B runs): 0 = the coefficient store of a step under `if ( emit )`, 1 = always at blk, 2 = at blk or at the sink */
-#endif
-#ifndef AA_STEP_PRELOAD
-#define AA_STEP_PRELOAD 1             /* build parameter (A/B runs): the step's LDS reads are asked for at the end of the previous step (tok::preload) */
-#endif
-
 namespace aa {
 
 struct alignas( 16 ) V16 { uint32_t x, y, z, w; };   // one 16-byte memory transaction
@@ -241,13 +225,12 @@ static_assert( kPlaneY % 8 == 0 && kPlaneUV % 8 == 0 && kPlaneY2 % 8 == 0 && kPl
 AA_HD constexpr uint32_t above_bytes( uint32_t mbw, bool shared ) { return shared ? 2u * mbw : mbw + ( mbw + 7u ) / 8u; }
 // then, only for frames with more than one token partition: 8 saved partition decoders x 16 bytes
 AA_HD constexpr uint32_t part_off( uint32_t mbw, bool shared ) { return ( kAbove + above_bytes( mbw, shared ) + 15 ) & ~15u; }
-// (AA_SLICE_SKEW: a slice of an ODD number of 16-byte units -- consecutive lanes' slices then start 4 * odd banks apart (8 different bank
-// phases) instead of 0 / 16 banks: lanes that read the same probability of their frames hit the same bank 4 ways instead of 15)
-AA_HD constexpr uint32_t slice_skew( uint32_t slice ) { return AA_SLICE_SKEW && ( slice / 16u ) % 2u == 0u ? 16u : 0u; }
 AA_HD constexpr uint32_t lane_lds_bytes( uint32_t mbw, bool multi_partition, bool shared = false )     // ring + slice
 {
-  return kRing + part_off( mbw, shared ) + ( multi_partition ? 128u : 0u ) + slice_skew( part_off( mbw, shared ) + ( multi_partition ? 128u : 0u ) );
+  return kRing + part_off( mbw, shared ) + ( multi_partition ? 128u : 0u );
 }
+// (Slices of an odd number of 16-byte units, to skew consecutive lanes against the LDS bank phases, were measured and changed nothing: the
+// conflicts are between lanes at different offsets)
 // (The flags were tried in HBM -- 240 bytes of LDS per lane at 1080p would buy 15 % more chains per CU --, the lane keeping the
 // eight columns it passes in registers.  Measured on MI355X, round 3: every use of those registers costs the wave an
 // s_waitcnt vmcnt(0), i.e. a drain of ALL its outstanding coefficient stores at every macroblock boundary of every lane;
@@ -469,12 +452,10 @@ struct Lane {
   Chunk16 pend[kChunks], mpend[kMetaChunks];
   // token in progress
   uint32_t rec;                   // address of the record of the node about to be decoded (>= R_MBDONE: an idle record -- not decoding)
-#if AA_STEP_PRELOAD
   // what the next step reads from LDS, asked for ahead of time (tok::preload): the probability at paddr, the stream byte at rpos, the
   // node record at rec, the band of the position after ia.  Whoever changes one of those four outside the step asks again.
   uint32_t pre_prob, pre_raw, pre_band;
   V8 pre_rec;
-#endif
   uint32_t paddr;                 // address of its probability
   uint32_t rowaddr, typeaddr;     // addresses of the current probability row / of this block type's probabilities
   uint32_t ia;                    // kBandTabOff + coefficient position (a multiple of 32 + position: shifts and `& 16` see the position)
@@ -669,17 +650,13 @@ AA_HD inline void store_mb_packed( const Frame & J, uint32_t mi, uint32_t nz_mas
 
 // The four LDS reads of a step (addresses all known when the previous step ends), asked for AHEAD of time -- at the end of the previous
 // step, in front of its coefficient store and bookkeeping, so that the round trip runs beside ~15 instructions instead of in front of
-// the step (a lone wave per SIMD has nobody else to hide it behind).  AA_STEP_PRELOAD=0: the step reads at its top (A/B builds).
+// the step (a lone wave per SIMD has nobody else to hide it behind).
 AA_HD inline void preload( Lane & L, uint8_t * smem )
 {
-#if AA_STEP_PRELOAD
   L.pre_prob = *lds_at<const uint8_t>( smem, L.paddr );
   L.pre_raw = *lds_at<const uint8_t>( smem, L.sbase | ( L.rpos & ( kRing - 1 ) ) );
   L.pre_rec = *lds_at<const V8>( smem, L.rec );
-  L.pre_band = *lds_at<const uint8_t>( smem, L.ia + 1u );
-#else
-  (void) L; (void) smem;
-#endif
+  L.pre_band = *lds_at<const uint8_t>( smem, L.ia + 1u );       // 33 * band of the NEXT position (the only one the row can move to)
 }
 
 // p + n words, n = 0 / 1, for a pointer into a coefficient chunk.  On the GPU a 32-bit add: a chunk is 64 KB and 64-KB aligned (the
@@ -942,15 +919,8 @@ AA_HD inline void step( Lane & L, uint8_t * smem, const Frame & J )
   (void) J;
   // EVERY lane runs the step (idle lanes: see "nodes" above); no condition, no branch, nothing predicated.  The LDS reads of a step;
   // all addresses were known at the end of the previous one
-#if AA_STEP_PRELOAD
   const uint32_t pbyte = L.pre_prob, raw = L.pre_raw, nband = L.pre_band;   // (asked for when the previous step -- or whoever moved the lane since -- knew the addresses)
   const V8 rec = L.pre_rec;
-#else
-  const uint32_t pbyte = *lds_at<const uint8_t>( smem, L.paddr );
-  const uint32_t raw = *lds_at<const uint8_t>( smem, L.sbase | ( L.rpos & ( kRing - 1 ) ) );
-  const V8 rec = *lds_at<const V8>( smem, L.rec );
-  const uint32_t nband = *lds_at<const uint8_t>( smem, L.ia + 1u );       // 33 * band of the NEXT position (the only one the row can move to)
-#endif
   const uint32_t was_idle = L.rec;              // (the record this step decodes: L.rec moves on below)
 
   // ... and while they travel: the renormalisation the previous step left undone (bool_decoder.hh:94-105; a lane's decoder is
@@ -959,7 +929,7 @@ AA_HD inline void step( Lane & L, uint8_t * smem, const Frame & J )
   L.range <<= ( shift & 31 );
   L.value <<= ( shift & 31 );
   L.sh += shift;
-#if AA_STEP_SCHED_BARRIER && defined( __HIP_DEVICE_COMPILE__ )
+#if defined( __HIP_DEVICE_COMPILE__ )
   // Everything above this line -- the previous step's coefficient store and bookkeeping, this step's renormalisation -- needs none of the
   // four values asked for by the previous step's preload(), everything below does: the scheduler keeps the two apart (left alone it has
   // put the first wait 8 instructions behind the reads and the independent work behind the wait: a lone wave per SIMD then sits the
@@ -997,7 +967,7 @@ AA_HD inline void step( Lane & L, uint8_t * smem, const Frame & J )
   const uint32_t pos = L.ia;                    // (the position of the token this step completes, if it does)
   L.rowaddr = rowaddr; L.paddr = paddr; L.rec = nextrec; L.ia = ia;
   preload( L, smem );                           // the next step's reads travel while this one stores its coefficient
-#if AA_STEP_SCHED_BARRIER && defined( __HIP_DEVICE_COMPILE__ )
+#if defined( __HIP_DEVICE_COMPILE__ )
   __builtin_amdgcn_sched_barrier( 0 );          // (... and nothing of what follows is done in front of them)
 #endif
 
@@ -1012,16 +982,10 @@ AA_HD inline void step( Lane & L, uint8_t * smem, const Frame & J )
     // values).  As `if ( emit )` it was the step's one predicated region -- an exec-mask save, a branch and a restore that nearly every
     // step of a wave of 30 lanes ran anyway, and a split of the step into basic blocks the scheduler could not move the LDS reads'
     // waits across (measured, session 13: the same source scheduled with the waits 17 instructions earlier was 6 % slower).
-#if AA_STEP_STORE_ALWAYS == 2
     // (... at the lane's sink when no token was completed: with every lane of the wave storing at its own block the store touched 30
     // cache lines a step instead of the ~6 of the lanes that have a value -- alone 8 % faster, beside the reconstruction kernels 5 %
     // slower than the predicated store, session 14)
     *( emit ? L.blk : L.sink ) = coeff;
-#elif AA_STEP_STORE_ALWAYS
-    *L.blk = coeff;
-#else
-    if ( emit ) *L.blk = coeff;
-#endif
     L.blk = bump_words( L.blk, emit );
     L.zzmask |= emit << ( pos & 31u );
   } else {
@@ -1092,9 +1056,7 @@ AA_HD inline void run_period( Lane & L, uint8_t * smem, const Frame & J, const H
     }
     const uint32_t it0 = it;
     do {
-#if AA_STEP_UNROLL
 #pragma unroll
-#endif
       for ( uint32_t k = 0; k < kBendEvery; k++ ) step<PK, MP>( L, smem, J );
       it += kBendEvery;
       // (asked by ALL lanes, outside the predicated regions: wave-uniform)
