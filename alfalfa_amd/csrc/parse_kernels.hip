@@ -205,8 +205,20 @@ __global__ __launch_bounds__( 64 ) void k_token_workers( const WorkerArgs a )
   bool retiring = false;                  // sticky: once the host has told this grid to retire, its waves take no more jobs
   // diagnostics: where a wave's time goes (100 MHz ticks): [0] boundary passes [1] their number [2] steps [3] looking for / starting
   // frames [4] ring top-ups [5] periods (hot loops + boundary passes) [6] lane-periods with a frame [7] periods
-  unsigned long long prof[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+  // (eight variables, not an array: an array that is indexed by a loop or handed on by address lives in private memory)
+  aa::tok::PeriodProf pp { 0, 0, 0 };       // [0] [1] [2]
+  unsigned long long p_look = 0, p_topup = 0, p_period = 0, p_lanes = 0, p_periods = 0;
   const bool profiling = a.prof != nullptr;
+  const auto prof_flush = [&]() {
+    __hip_atomic_fetch_add( &a.prof[0], pp.pass_ticks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+    __hip_atomic_fetch_add( &a.prof[1], pp.passes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+    __hip_atomic_fetch_add( &a.prof[2], pp.steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+    __hip_atomic_fetch_add( &a.prof[3], p_look, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+    __hip_atomic_fetch_add( &a.prof[4], p_topup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+    __hip_atomic_fetch_add( &a.prof[5], p_period, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+    __hip_atomic_fetch_add( &a.prof[6], p_lanes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+    __hip_atomic_fetch_add( &a.prof[7], p_periods, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+  };
   for ( ;; ) {
     const unsigned long long t_a = profiling ? wall_clock64() : 0ull;
     const bool idle = is_lane && L.rec == aa::tok::R_DONE;
@@ -282,20 +294,20 @@ __global__ __launch_bounds__( 64 ) void k_token_workers( const WorkerArgs a )
     const unsigned long long t_b = profiling ? wall_clock64() : 0ull;
     if ( active ) aa::tok::top_up<MP>( L, smem, F );
     const unsigned long long t_c = profiling ? wall_clock64() : 0ull;
-    aa::tok::run_period<PK, MP>( L, smem, F, a.heap, profiling ? prof : nullptr );
+    aa::tok::run_period<PK, MP>( L, smem, F, a.heap, profiling, pp );
     if ( profiling ) {
       const unsigned long long t_d = wall_clock64();
-      prof[3] += t_b - t_a; prof[4] += t_c - t_b; prof[5] += t_d - t_c;
-      prof[6] += static_cast<unsigned long long>( __popcll( __ballot( active ) ) ); prof[7]++;
+      p_look += t_b - t_a; p_topup += t_c - t_b; p_period += t_d - t_c;
+      p_lanes += static_cast<unsigned long long>( __popcll( __ballot( active ) ) ); p_periods++;
       // (waves stay for as long as there is work: the sums go out every 1024 periods, not only when the wave leaves)
-      if ( ( prof[7] & 1023ull ) == 0 ) {
-        if ( lane == 0 ) for ( int k = 0; k < 8; k++ ) __hip_atomic_fetch_add( &a.prof[k], prof[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-        for ( int k = 0; k < 8; k++ ) prof[k] = 0;
+      if ( ( p_periods & 1023ull ) == 0 ) {
+        if ( lane == 0 ) prof_flush();
+        pp = { 0, 0, 0 }; p_look = p_topup = p_period = p_lanes = p_periods = 0;
       }
     }
   }
   if ( lane == 0 ) {
-    if ( profiling ) for ( int k = 0; k < 8; k++ ) __hip_atomic_fetch_add( &a.prof[k], prof[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+    if ( profiling ) prof_flush();
     if ( a.cu_slots ) AA_AT_ADD( &a.cu_slots[cu_slot], 0xFFFFFFFFu );
     AA_AT_ADD( a.exited, 1u );
   }

@@ -468,6 +468,10 @@ struct Lane {
   uint32_t ctxbits;               // non-zero flags: above (this column) bits 0-8, left bits 16-24
   uint32_t flags, nz_mask, mb_first, coeff_blocks, yfirst;
   uint32_t ykind;                 // which Y plane the slice holds (Y_AFTER_Y2 / Y_WITHOUT_Y2; kNoPlane: none yet)
+  // a lane of its own (the kernels without a lane per partition): what the boundary pass would otherwise wait for
+  uint32_t y2byte;                // the byte of the above-row Y2 bit array that holds column `col` (columns col & ~7 ..), as the array has it
+  uint32_t nx_mi;                 // the macroblock the three values below were read for at the end of the one before it (kNoPend: none)
+  uint32_t nx_flags, nx_above, nx_y2;   // its flags byte, the above Y/U/V flags of its column, the Y2 bit byte of its column
   AA_GLOBAL int16_t * blk;        // the coefficient block being filled = Heap::base + 16 * blk_index (zeroed in advance)
   uint32_t blk_index;             // its index in the heap
   uint32_t blk_left;              // blocks left in the chunk being filled, the current one included (0: no chunk yet)
@@ -672,20 +676,23 @@ AA_HD inline AA_GLOBAL int16_t * bump_words( AA_GLOBAL int16_t * p, uint32_t n )
 #endif
 }
 
-// Make block `blk` of the macroblock the current one: contexts from the non-zero flags, first probability row.
-AA_HD inline void setup_block( Lane & L, const uint8_t * smem, uint32_t blk )
+// Make the macroblock's FIRST block the current one: contexts from the non-zero flags, first probability row.  Which block that is follows
+// from the flags byte alone -- the Y2 block, or the first Y block of a macroblock without one --, so its block-table entry is one of two
+// constants and no LDS read stands between the flags and the first node's reads (both start at position 0: only Y blocks AFTER a Y2
+// start at 1, tokens.cc:61).
+AA_HD inline void setup_first_block( Lane & L, uint32_t has_y2 )
 {
-  const V8 e = *reinterpret_cast<const V8 *>( smem + kBlockTabOff + 8 * blk );
-  const uint32_t sel = ( e.x >> 16 ) & 255u;
-  L.blkaddr = kBlockTabOff + 8 * ( blk + 1 );
-  L.nzsel = e.y;
-  L.blkslot = e.x >> 24;
+  constexpr V8 e0 = kBlockTable.b[0], e1 = kBlockTable.b[1];
+  static_assert( ( ( e0.x >> 16 ) & 255u ) == kPlaneY2 / 8 && ( ( e1.x >> 16 ) & 255u ) == kPlaneY / 8 + kBlkIsY, "first blocks: Y2 / Y" );
+  const bool y2 = has_y2 != 0u;
+  L.blkaddr = kBlockTabOff + ( y2 ? 8u : 16u );
+  L.nzsel = y2 ? e0.y : e1.y;
+  L.blkslot = y2 ? e0.x >> 24 : e1.x >> 24;
   L.blkbit = 1u << L.blkslot;
-  const uint32_t ctx = AA_POPC( L.ctxbits & e.y );          // "above" flag + "left" flag
-  L.typeaddr = L.base + 8u * ( sel & ( kBlkIsY - 1u ) );
-  const uint32_t idx = ( sel & kBlkIsY ) ? L.yfirst : 0u;   // Y blocks after a Y2 start at position 1 (tokens.cc:61)
-  L.ia = kBandTabOff + idx;
-  L.rowaddr = L.typeaddr + idx * 33u + ctx * 11u;           // band of position 0 / 1 is 0 / 1
+  const uint32_t ctx = AA_POPC( L.ctxbits & L.nzsel );      // "above" flag + "left" flag
+  L.typeaddr = L.base + ( y2 ? kPlaneY2 : kPlaneY );
+  L.ia = kBandTabOff;
+  L.rowaddr = L.typeaddr + ctx * 11u;                       // band of position 0 is 0
   L.rec = 0; L.paddr = L.rowaddr;
   L.nonzero = 0; L.mag = 0;
 }
@@ -755,32 +762,45 @@ AA_HD inline void finish_partition( Lane & L, uint8_t * smem, const Frame & J, c
 
 // ---- the above-row non-zero flags of column `col` (9 bits: ctxbits bits 0-8); `abase` = address of the array -----------------
 template <bool SH>
-AA_HD inline uint32_t above_load( uint8_t * smem, uint32_t abase, uint32_t mbw, uint32_t col )
+AA_HD inline uint32_t above_load( uint8_t * smem, uint32_t abase, uint32_t mbw, uint32_t col, uint32_t & y2byte )
 {
   if constexpr ( SH ) return *lds_at<const uint16_t>( smem, abase + 2u * col );
   else {
-    const uint32_t yuv = *lds_at<const uint8_t>( smem, abase + col ), y2 = *lds_at<const uint8_t>( smem, abase + mbw + ( col >> 3 ) );
-    return yuv | ( ( ( y2 >> ( col & 7u ) ) & 1u ) << 8 );
+    const uint32_t yuv = *lds_at<const uint8_t>( smem, abase + col );
+    y2byte = *lds_at<const uint8_t>( smem, abase + mbw + ( col >> 3 ) );
+    return yuv | ( ( ( y2byte >> ( col & 7u ) ) & 1u ) << 8 );
   }
 }
+// (a lane of its own keeps the Y2 byte of its column in a register, Lane::y2byte: nobody else touches the byte, so the bit goes
+// into the register and the byte is stored -- no read-modify-write, nothing to wait for)
 template <bool SH>
-AA_HD inline void above_store( uint8_t * smem, uint32_t abase, uint32_t mbw, uint32_t col, uint32_t bits )
+AA_HD inline void above_store( uint8_t * smem, uint32_t abase, uint32_t mbw, uint32_t col, uint32_t bits, uint32_t & y2byte )
 {
   if constexpr ( SH ) *lds_at<uint16_t>( smem, abase + 2u * col ) = static_cast<uint16_t>( bits );
   else {
     *lds_at<uint8_t>( smem, abase + col ) = static_cast<uint8_t>( bits );
-    const uint32_t at = abase + mbw + ( col >> 3 ), m = 1u << ( col & 7u );      // (this lane's own array: nobody else touches the byte)
-    const uint32_t old = *lds_at<const uint8_t>( smem, at );
-    *lds_at<uint8_t>( smem, at ) = static_cast<uint8_t>( ( bits & 0x100u ) ? old | m : old & ~m );
+    const uint32_t m = 1u << ( col & 7u );
+    y2byte = ( bits & 0x100u ) ? y2byte | m : y2byte & ~m;
+    *lds_at<uint8_t>( smem, abase + mbw + ( col >> 3 ) ) = static_cast<uint8_t>( y2byte );
   }
 }
 
-// plane `type` of the frame's token probabilities -> the slice's plane at `off` (66 words; the job's table is in HBM)
+// plane `type` of the frame's token probabilities -> the slice's plane at `off` (66 words; the job's table is in HBM).  ROUNDS = 1: all
+// 66 reads in flight at once, one trip to HBM -- the boundary pass, where the whole wave waits for it.  At the start of a frame, where two
+// planes are read back to back, that is 132 registers in flight and was the kernel's register peak: there each plane goes in three rounds.
+template <uint32_t ROUNDS = 1>
 AA_HD inline void load_plane( uint8_t * smem, uint32_t at, const Frame & J, uint32_t type )
 {
+  constexpr uint32_t per = kPlaneBytes / 4 / ROUNDS;
+  static_assert( per * ROUNDS * 4 == kPlaneBytes, "whole rounds" );
   const AA_GLOBAL uint32_t * src = (const AA_GLOBAL uint32_t *) &J.job->fp.coeff_probs[type][0][0][0];
   auto dst = lds_at<uint32_t>( smem, at );
-  for ( uint32_t k = 0; k < kPlaneBytes / 4; k++ ) dst[k] = src[k];
+  if constexpr ( ROUNDS == 1 ) { for ( uint32_t k = 0; k < per; k++ ) dst[k] = src[k]; }
+  else {
+    _Pragma( "unroll 1" )
+    for ( uint32_t r = 0; r < ROUNDS; r++ )
+      for ( uint32_t k = 0; k < per; k++ ) dst[r * per + k] = src[r * per + k];
+  }
 }
 
 constexpr unsigned long long kMemWaitTicks = 200000000ull;      // 2 s of the 100 MHz clock: then the frame is handed back (TOK_NO_MEMORY)
@@ -790,6 +810,15 @@ constexpr unsigned long long kMemWaitTicks = 200000000ull;      // 2 s of the 10
 // (mi, col, row, the non-zero flags); what follows from the verdict is straight-line code behind the loop.  With the set-up inside
 // the loop (every exit a `return`) the compiler carried every field of the lane any exit writes through the loop's merge points:
 // ~85 register copies per pass, each an issue slot of the whole wave.
+//
+// LDS round trips of the pass.  A lane of its own (MP == false), on the common path -- a coded macroblock behind a coded macroblock of
+// the same row --, waits for no read the pass itself issues: the Y2 bit goes into Lane::y2byte and the byte is stored without being read;
+// the flags byte, the above flags and the Y2 byte of the next column were asked for by the block-end pass that completed the macroblock
+// (Lane::nx_*); the first block's table entry is a constant (setup_first_block).  What remains is the wait for those early values and
+// the first node's reads, which the step waits for.  The first macroblock of a row, one behind a skipped macroblock and one the flag
+// ring did not hold in time read flags, above byte and Y2 byte in the pass: one trip more.  With a lane per partition (MP == true: the
+// above flags are uint16 per column in an array a neighbour lane writes, and a progress word says when) the reads stay in the pass --
+// progress word, flags + above flags, then the first node's reads; only the block-table read is gone.
 template <bool PK, bool MP = false>
 AA_HD inline void macroblock_boundary_body( Lane & L, uint8_t * smem, const Frame & J, const Heap & H )
 {
@@ -801,7 +830,7 @@ AA_HD inline void macroblock_boundary_body( Lane & L, uint8_t * smem, const Fram
     return;
   }
   if ( L.rec == R_MBDONE ) {
-    above_store<MP>( smem, above, J.mbw, L.col, L.ctxbits );           // the column's flags as the macroblock leaves them
+    above_store<MP>( smem, above, J.mbw, L.col, L.ctxbits, L.y2byte );      // the column's flags as the macroblock leaves them
     L.mi++; L.col++; L.rec = R_MB;
     if constexpr ( MP ) { L.mi_real++; if ( mp ) *lds_at<uint32_t>( smem, shared + 4 * J.mp_p ) = L.mi; }       // completed: the row below may follow
   }
@@ -823,12 +852,22 @@ AA_HD inline void macroblock_boundary_body( Lane & L, uint8_t * smem, const Fram
       const uint32_t q = J.mp_p ? J.mp_p - 1u : J.mp_P - 1u, k = J.mp_p ? L.row : L.row - 1u;
       if ( AA_LDS_LOAD( smem, shared + 4 * q ) < k * J.mbw + L.col + 1u ) break;      // not there yet: ask again at the next pass
     }
-    flags = smem[L.base + kMeta + ( L.mi & ( kMetaRing - 1 ) )];
-    L.ctxbits = ( L.ctxbits & 0x01FF0000u ) | above_load<MP>( smem, above, J.mbw, L.col );
+    uint32_t up;
+    if ( !MP && L.nx_mi == L.mi ) {
+      // asked for when the macroblock before this one ended (block_end): nothing to wait for.  The Y2 byte is the one in the
+      // register unless this column starts a new one.
+      flags = L.nx_flags;
+      L.y2byte = ( L.col & 7u ) ? L.y2byte : L.nx_y2;
+      up = L.nx_above | ( ( ( L.y2byte >> ( L.col & 7u ) ) & 1u ) << 8 );
+    } else {
+      flags = smem[L.base + kMeta + ( L.mi & ( kMetaRing - 1 ) )];
+      up = above_load<MP>( smem, above, J.mbw, L.col, L.y2byte );
+    }
+    L.ctxbits = ( L.ctxbits & 0x01FF0000u ) | up;
     if ( !( flags & AA_MB_SKIP ) ) { verdict = V_CODED; break; }
     const uint32_t has_y2 = flags & AA_MB_HAS_Y2;
     L.ctxbits &= has_y2 ? 0u : 0x01000100u;                 // a non-coded Y2 leaves its chain untouched (frame.cc:255-269)
-    above_store<MP>( smem, above, J.mbw, L.col, L.ctxbits );
+    above_store<MP>( smem, above, J.mbw, L.col, L.ctxbits, L.y2byte );
     const uint32_t mi_rec = MP ? L.mi_real : L.mi;
     if constexpr ( PK ) store_mb_packed( J, mi_rec, 0, 0, flags | ( has_y2 ? AA_MB_LF_SKIP_INNER : 0u ) );
     else store_mb( J, mi_rec, 0, L.blk_index, flags | ( has_y2 ? AA_MB_LF_SKIP_INNER : 0u ) );
@@ -884,9 +923,11 @@ AA_HD inline void macroblock_boundary_body( Lane & L, uint8_t * smem, const Fram
   } else L.mb_first = L.blk_index;
   L.flags = flags; L.nz_mask = 0;
   const uint32_t kind = has_y2 ? Y_AFTER_Y2 : Y_WITHOUT_Y2;
-  if ( L.ykind != kind ) { load_plane( smem, L.base + kPlaneY, J, kind ); L.ykind = kind; }
+  // (dense storage: in two rounds -- with all 66 reads in flight that instantiation needs more than the 256 registers that let another
+  // kernel's wave share the SIMD; packed storage, the format made for throughput, keeps the single trip)
+  if ( L.ykind != kind ) { load_plane<PK ? 1 : 2>( smem, L.base + kPlaneY, J, kind ); L.ykind = kind; }
   L.yfirst = has_y2 ? 1u : 0u;
-  setup_block( L, smem, has_y2 ? 0u : 1u );
+  setup_first_block( L, has_y2 );
 }
 
 template <bool PK, bool MP = false>
@@ -1020,6 +1061,18 @@ AA_HD inline void block_end( Lane & L, uint8_t * smem, const Frame & J, const He
         store_mb_packed( J, MP ? L.mi_real : L.mi, L.nz_mask, L.mb_first, flags, static_cast<unsigned long long>( L.hdr - H.base ) );
         if ( !L.nz_mask ) L.blk = L.hdr;      // coded, and every block empty: the mask slots go back (the macroblock stores nothing)
       } else store_mb( J, MP ? L.mi_real : L.mi, L.nz_mask, L.mb_first, flags );
+      if constexpr ( !MP ) {
+        // what the boundary pass needs of the NEXT macroblock, asked for now: its flags byte, the above flags of its column, the Y2
+        // byte of that column (which the pass takes only where the column starts a new byte).  Not when the row ends here or the
+        // flag ring does not hold the macroblock yet: the pass then reads for itself.
+        const uint32_t nmi = L.mi + 1u, ncol = L.col + 1u;
+        const bool ok = nmi < L.mwpos && ncol < J.mbw;
+        const uint32_t c = ok ? ncol : 0u;
+        L.nx_flags = *lds_at<const uint8_t>( smem, L.base + kMeta + ( nmi & ( kMetaRing - 1 ) ) );
+        L.nx_above = *lds_at<const uint8_t>( smem, L.base + kAbove + c );
+        L.nx_y2 = *lds_at<const uint8_t>( smem, L.base + kAbove + J.mbw + ( c >> 3 ) );
+        L.nx_mi = ok ? nmi : kNoPend;
+      }
     }
     // the block after it (never a Y2)
     const uint32_t sel = AA_UBFE( nextblk.x, 16, 8 );
@@ -1041,16 +1094,19 @@ AA_HD inline void block_end( Lane & L, uint8_t * smem, const Frame & J, const He
 
 // One period of a wave: kPeriod steps in groups of kBendEvery, each group followed by the block-end pass if a lane waits for
 // one; the hot loop is left whenever a lane has reached a macroblock boundary (which only a block-end pass can bring about).
-// `prof` (diagnostics, may be null): [0] += clock ticks spent in boundary passes, [1] += boundary passes, [2] += steps of the wave
+// Diagnostics (`profiling`): clock ticks spent in boundary passes, their number, steps of the wave.  The three sums are the caller's own
+// variables, handed in by reference and touched only when `profiling` is set: as elements of an array reached through a pointer that
+// may be null they stayed in private memory -- a scratch allocation for the kernel whether it profiled or not.
+struct PeriodProf { unsigned long long pass_ticks, passes, steps; };
 template <bool PK, bool MP = false>
-AA_HD inline void run_period( Lane & L, uint8_t * smem, const Frame & J, const Heap & H, unsigned long long * prof = nullptr )
+AA_HD inline void run_period( Lane & L, uint8_t * smem, const Frame & J, const Heap & H, bool prof, PeriodProf & P )
 {
   uint32_t it = 0;
   while ( it < kPeriod ) {
     if ( AA_ANY( at_boundary<MP>( L ) ) ) {
       const unsigned long long tb = prof ? AA_NOW() : 0ull;
       if ( at_boundary<MP>( L ) ) macroblock_boundary<PK, MP>( L, smem, J, H );
-      if ( prof ) { prof[0] += AA_NOW() - tb; prof[1]++; }
+      if ( prof ) { P.pass_ticks += AA_NOW() - tb; P.passes++; }
       it++;                                                 // (a lane waiting for flags must not spin the period away)
       if ( !AA_ANY( L.rec < R_MBDONE ) ) break;             // nobody has anything to decode (no lane is at R_BEND out here)
     }
@@ -1062,9 +1118,15 @@ AA_HD inline void run_period( Lane & L, uint8_t * smem, const Frame & J, const H
       // (asked by ALL lanes, outside the predicated regions: wave-uniform)
       if ( AA_ANY( L.rec == R_BEND ) ) block_end<PK, MP>( L, smem, J, H );
     } while ( it < kPeriod && !AA_ANY( L.rec == R_MBDONE ) );
-    if ( prof ) prof[2] += it - it0;
+    if ( prof ) P.steps += it - it0;
   }
   if ( L.rec != R_DONE ) L.steps += it;                     // (an upper bound: the iterations a lane sat out count too)
+}
+template <bool PK, bool MP = false>
+AA_HD inline void run_period( Lane & L, uint8_t * smem, const Frame & J, const Heap & H )
+{
+  PeriodProf none { 0, 0, 0 };
+  run_period<PK, MP>( L, smem, J, H, false, none );
 }
 
 // ---- a lane's life ---------------------------------------------------------------------------------------------------
@@ -1098,6 +1160,7 @@ AA_HD inline void init_lane( Lane & L, uint32_t sbase, uint32_t base, AA_GLOBAL 
   L.value = 0; L.range = 255; L.sh = 0; L.rpos = 0; L.mag = 0; L.zzmask = 0; L.nonzero = 0;
   L.blk = sink; L.hdr = nullptr;
   L.pend_wpos = L.pend_mwpos = kNoPend;
+  L.y2byte = 0; L.nx_mi = kNoPend; L.nx_flags = L.nx_above = L.nx_y2 = 0;
   L.steps = 0;
 }
 
@@ -1110,8 +1173,8 @@ AA_HD inline void begin_frame( Lane & L, uint8_t * smem, uint32_t base, const Fr
   // flags / partition save area
   L.base = base;
   uint8_t * lds = smem + base;
-  load_plane( smem, base + kPlaneUV, J, UV );
-  load_plane( smem, base + kPlaneY2, J, Y2 );
+  load_plane<3>( smem, base + kPlaneUV, J, UV );
+  load_plane<3>( smem, base + kPlaneY2, J, Y2 );
   L.ykind = kNoPlane;
   if ( J.nparts > 1 ) for ( uint32_t k = 0; k < 128 / 4; k++ ) reinterpret_cast<uint32_t *>( lds + part_off( J.mbw, SH ) )[k] = 0;
   for ( uint32_t k = 0; k < above_bytes( J.mbw, SH ); k++ ) lds[kAbove + k] = 0;
@@ -1124,6 +1187,7 @@ AA_HD inline void begin_frame( Lane & L, uint8_t * smem, uint32_t base, const Fr
   L.blk = L.sink; L.blk_index = 0; L.blk_left = 0; L.nchunks = 0; L.mem_since = 0;     // the first coded macroblock takes the first chunk
   L.hdr = nullptr; L.zzmask = 0; L.words = 0;
   L.mi_real = 0; L.chunk_ord = 0;
+  L.y2byte = 0; L.nx_mi = kNoPend;
   if ( J.mp_P > 1 ) {
     // one lane per partition: this lane's first row is row mp_p; the owner's slice holds what the lanes share
     L.mi_real = J.mp_p * J.mbw;
