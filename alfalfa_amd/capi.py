@@ -74,6 +74,13 @@ class RgbTarget(C.Structure):
     _fields_ = [("dst", C.c_void_p), ("row_stride", C.c_int64), ("plane_stride", C.c_int64)]
 
 
+AA_QUALITY_Y, AA_QUALITY_YUV = 1, 3
+
+
+class QualityRef(C.Structure):
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("y_stride", C.c_int64), ("uv_stride", C.c_int64)]
+
+
 class AlfalfaError(RuntimeError):
     """Mirrors the reference's exception types (exception.hh:76-98) by name in `.kind`."""
 
@@ -128,6 +135,7 @@ SYMBOLS = [
     ("aa_stream_raster_device", C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     ("aa_render_rgb_async", C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(RgbTarget),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    ("aa_quality_batch_async", C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.POINTER(QualityRef), C.c_int, _P, _P, _P]),
     ("aa_stream_references", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("aa_stream_reference_slots", C.c_int, [_P, C.POINTER(C.c_int)]),
     ("aa_stream_import_reference", C.c_int, [_P, _P, _P, _P]),

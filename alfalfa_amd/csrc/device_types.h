@@ -49,6 +49,19 @@ struct aa_rgb_job {
   uint32_t pad;
 };
 
+// One plane of one pair on its way to a score (aa_quality_batch_async): a = the decoded plane, b = the original's
+#define AA_QUALITY_STRIP_ROWS 8        // window rows per workgroup of k_quality_blocks
+#define AA_QUALITY_CHUNK_WINDOWS 480   // ... and windows per row it holds; wider planes are cut into column chunks
+struct aa_quality_job {
+  const uint8_t * a, * b;
+  int64_t stride_a, stride_b;  // bytes
+  uint32_t w4, h4;             // 4x4 blocks per row and per column of the padded plane
+  uint32_t groups;             // groups of four windows per window row: (w4 - 1 + 3) / 4
+  uint32_t strips, chunks;     // workgroups: strips of AA_QUALITY_STRIP_ROWS window rows x column chunks
+  uint32_t pad;
+  uint64_t out_off;            // the plane's first group value in the workspace (floats; a multiple of 4)
+};
+
 #define AA_MAX_XCD 16
 
 #define AA_SYNC_WS_DUMP 140
@@ -133,4 +146,7 @@ int launch_render_rgb( const aa_rgb_job * jobs, int n, int format, const uint32_
 // dst = src with lf_level := byte `segment_id` of `levels` (records are 80 bytes, 16-byte aligned)
 int launch_lf_relevel( const aa_mb_info * src, aa_mb_info * dst, unsigned nmb, uint32_t levels, void * stream );
 int launch_ssim_windows( const uint8_t * a, const uint8_t * b, int width, int height, float * out, void * stream );
+// quality_kernels.hip: jobs[i] (n_planes of them) -> ssim[i], sse[i] (optional; zeroed by the caller): k_quality_blocks over
+// max_blocks x n_planes workgroups (max_blocks: the largest job's strips * chunks), then k_quality_sum; group_values: the workspace
+int launch_quality( const aa_quality_job * jobs, int n_planes, uint32_t max_blocks, float * group_values, double * ssim, unsigned long long * sse, void * stream );
 }

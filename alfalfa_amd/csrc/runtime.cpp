@@ -41,7 +41,7 @@
 #include "tok_fsm.hh"
 #include "coeff_pack.hh"
 
-// ONE translation unit, nine source files (round 6; the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
+// ONE translation unit, ten source files (round 6; the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
 // the pieces share file-local state (the anonymous-namespace helpers, g_last_error) and are #included in dependency order.
 #include "runtime_types.inc"
 #include "runtime_pool.inc"
@@ -51,4 +51,5 @@
 #include "runtime_submit.inc"
 #include "runtime_decode.inc"
 #include "runtime_rasters.inc"
+#include "runtime_quality.inc"
 #include "runtime_lf_search.inc"

@@ -217,6 +217,10 @@ static void ctx_free( aa_ctx * ctx )
     if ( rb.dev ) (void) hipFree( rb.dev );
     for ( hipEvent_t e : { rb.done, rb.before, rb.after } ) if ( e ) (void) hipEventDestroy( e );
   }
+  for ( auto & qb : ctx->quality_bufs ) {
+    if ( qb.host ) (void) hipHostFree( qb.host );
+    for ( hipEvent_t e : { qb.done, qb.before, qb.after } ) if ( e ) (void) hipEventDestroy( e );
+  }
   if ( ctx->ws ) (void) hipFree( ctx->ws );
   if ( ctx->boundary ) (void) hipFree( ctx->boundary );
   tok_free( ctx );

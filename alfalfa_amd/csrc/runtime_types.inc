@@ -180,6 +180,9 @@ struct aa_ctx {
   struct RgbBuf { uint8_t * host = nullptr, * dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr, before = nullptr, after = nullptr; bool busy = false; };
   RgbBuf rgb_bufs[kBindBufs];
   int next_rgb_buf = 0;
+  // the job table of a scoring call (aa_quality_batch_async): written to `host`, copied into the call's pool piece (`dev` stays null)
+  RgbBuf quality_bufs[kBindBufs];
+  int next_quality_buf = 0;
   int row_handoff_by_kernel[2] = { 0, 0 };   // (diagnostics: waits the second look ended, k_recon_intra4 / k_loopfilter_rows4)
   std::deque<int> downloads_in_flight;   // gather_bufs whose copy (aa_download_batch_async) nobody has waited for yet, oldest first
   // A parse batch holds its stream for as long as its longest chain (seconds for a key frame): a batch queued behind another

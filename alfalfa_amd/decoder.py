@@ -5,6 +5,7 @@ Decoder ~ Decoder (decoder.hh:244-300: decode_frame / get_frame_output / parse_a
 get_references), FilePlayer ~ FilePlayer (player.hh:66-97: advance / eof), DecodeBatch = N
 independent streams decoded in lockstep (ExCamera chunks / GOPs, one batch per GPU).
 """
+import collections
 import ctypes as C
 import struct
 
@@ -12,6 +13,9 @@ import numpy as np
 
 from . import capi
 from .capi import AlfalfaError, FrameHeader, MB_INFO_DTYPE  # noqa: F401
+
+
+Quality = collections.namedtuple("Quality", ["ssim", "sse"])
 
 
 class Parser:
@@ -274,6 +278,82 @@ class Context:
             cur.wait_stream(compute)
         return result
 
+    QUALITY_PLANES = {"y": capi.AA_QUALITY_Y, "yuv": capi.AA_QUALITY_YUV}
+
+    def quality(self, decoders, frame_indices, originals, planes="y", out=None):
+        """Frame frame_indices[i] of decoders[i] scored against originals[i] on this context's device (aa_quality_batch_async):
+        BaseRaster::quality -- x264's SSIM, the value aa_ssim_host gives, bit for bit -- and the sum of squared differences, per plane
+        over the PADDED planes.  planes: "y" or "yuv".  originals[i]: a tuple (y, u, v) of uint8 device tensors of the padded plane
+        shapes (u, v may be None for "y"; views with padded rows are accepted, the innermost stride must be 1), or a pair
+        (decoder, frame_index) for decoded against decoded.
+        -> Quality(ssim: float64 (N, P), sse: int64 (N, P)), ordered on torch.cuda.current_stream() like to_rgb's result; out: a pair
+        of such tensors (contiguous) to write into."""
+        import torch
+        if planes not in self.QUALITY_PLANES:
+            raise ValueError("quality: planes must be \"y\" or \"yuv\", not %r" % (planes,))
+        np_ = self.QUALITY_PLANES[planes]
+        n = len(decoders)
+        if n == 0 or len(frame_indices) != n or len(originals) != n:
+            raise ValueError("quality: need as many frame indices and originals as decoders, and at least one")
+        device = torch.device("cuda", self.device)
+        if out is None:
+            ssim = torch.empty((n, np_), dtype=torch.float64, device=device)
+            sse = torch.empty((n, np_), dtype=torch.int64, device=device)
+        else:
+            ssim, sse = out
+            for name, t, dt in (("ssim", ssim, torch.float64), ("sse", sse, torch.int64)):
+                if tuple(t.shape) != (n, np_) or t.dtype != dt or t.device != device or not t.is_contiguous():
+                    raise ValueError("quality: out %s must be a contiguous %s tensor of shape %s on %s" % (name, dt, (n, np_), device))
+        refs = (capi.QualityRef * n)()
+        keep = []
+        for i, (d, o) in enumerate(zip(decoders, originals)):
+            if len(o) == 2 and isinstance(o[0], Decoder):
+                od, ofi = o
+                if (od.padded_width, od.padded_height) != (d.padded_width, d.padded_height):
+                    raise ValueError("quality: originals[%d] is a frame of %dx%d padded, expected %dx%d"
+                                     % (i, od.padded_width, od.padded_height, d.padded_width, d.padded_height))
+                if od.ctx is not self:
+                    raise ValueError("quality: originals[%d] is a decoder of another context" % i)
+                if not 0 <= ofi < od.frame_count():
+                    raise ValueError("quality: originals[%d]: bad frame index %d" % (i, ofi))
+                refs[i].y, refs[i].u, refs[i].v = od.raster_device_pointers(ofi)
+                refs[i].y_stride, refs[i].uv_stride = d.padded_width, d.padded_width // 2
+                continue
+            if len(o) != 3:
+                raise ValueError("quality: originals[%d] must be (y, u, v) or (decoder, frame_index)" % i)
+            ptrs, strides = [None] * 3, [0, 0, 0]
+            for p, t in enumerate(o):
+                if p >= np_:
+                    break
+                shape = (d.padded_height, d.padded_width) if p == 0 else (d.padded_height // 2, d.padded_width // 2)
+                if t is None:
+                    raise ValueError("quality: originals[%d]: plane %d is None" % (i, p))
+                if tuple(t.shape) != shape:
+                    raise ValueError("quality: originals[%d]: plane %d has shape %s, expected %s" % (i, p, tuple(t.shape), shape))
+                if t.dtype != torch.uint8 or t.device != device:
+                    raise ValueError("quality: originals[%d]: plane %d is %s on %s, expected torch.uint8 on %s" % (i, p, t.dtype, t.device, device))
+                if t.stride(1) != 1 or t.stride(0) < shape[1]:
+                    raise ValueError("quality: originals[%d]: plane %d: the rows must be contiguous and must not overlap" % (i, p))
+                ptrs[p], strides[p] = t.data_ptr(), t.stride(0)
+                keep.append(t)
+            if np_ == 3 and strides[1] != strides[2]:
+                raise ValueError("quality: originals[%d]: u and v must have the same row stride" % i)
+            refs[i].y, refs[i].u, refs[i].v = ptrs
+            refs[i].y_stride, refs[i].uv_stride = strides[0], strides[1]
+        arr = (C.c_void_p * n)(*[d.h for d in decoders])
+        idx = (C.c_int * n)(*frame_indices)
+        cur = torch.cuda.current_stream(device)
+        compute = None
+        if not cur.cuda_stream:
+            # (the null stream's handle means "no consumer stream" to the C call: the two waits are made through torch, as in to_rgb)
+            compute = torch.cuda.ExternalStream(self.compute_stream(), device=device)
+            compute.wait_stream(cur)
+        capi.check(self.L.aa_quality_batch_async(self.h, arr, n, idx, refs, np_, C.c_void_p(ssim.data_ptr()), C.c_void_p(sse.data_ptr()),
+                                                 C.c_void_p(cur.cuda_stream or None)))
+        if compute is not None:
+            cur.wait_stream(compute)
+        return Quality(ssim, sse)
+
     def decode_batch(self, decoders, frame_indices):
         n = len(decoders)
         arr = (C.c_void_p * n)(*[d.h for d in decoders])
@@ -434,6 +514,11 @@ class Decoder:
         """One frame as RGB on the device (Context.to_rgb): (H, W, 3|4) or (3, H, W); out: a tensor of that shape."""
         return self.ctx.to_rgb([self], [frame_index], format, mean, std, None if out is None else [out])[0]
 
+    def quality(self, frame_index, original, planes="y"):
+        """One frame against its original on the device (Context.quality) -> Quality(ssim (P,), sse (P,))."""
+        q = self.ctx.quality([self], [frame_index], [original], planes)
+        return Quality(q.ssim[0], q.sse[0])
+
     def raster_device_pointers(self, frame_index):
         y, u, v = C.c_void_p(), C.c_void_p(), C.c_void_p()
         capi.check(self.L.aa_stream_raster_device(self.h, frame_index, C.byref(y), C.byref(u), C.byref(v)))
@@ -479,6 +564,16 @@ class Decoder:
     def import_reference_host(self, y, u, v):
         y, u, v = (np.ascontiguousarray(p, dtype=np.uint8) for p in (y, u, v))
         capi.check(self.L.aa_stream_import_reference_host(self.h, y.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)))
+
+
+def psnr(sse, width, height, planes):
+    """10 log10(255^2 pixels / sse) of Quality.sse (torch, (..., P)) for padded planes of width x height luma pixels: planes "y" or
+    "yuv" (chroma planes hold a quarter of the pixels); inf where sse == 0."""
+    import torch
+    pixels = [float(width * height)] + [float((width // 2) * (height // 2))] * 2
+    count = torch.tensor(pixels[:Context.QUALITY_PLANES[planes]], dtype=torch.float64, device=sse.device)
+    s = sse.to(torch.float64)
+    return torch.where(s == 0, torch.full_like(s, float("inf")), 10.0 * torch.log10(255.0 * 255.0 * count / s))
 
 
 def read_ivf(path_or_bytes):

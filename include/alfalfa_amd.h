@@ -367,6 +367,22 @@ enum { AA_RGB_U8_HWC3 = 0, AA_RGB_U8_HWC4 = 1, AA_RGB_U8_CHW = 2, AA_RGB_F16_CHW
 typedef struct aa_rgb_target { void * dst; int64_t row_stride; int64_t plane_stride; } aa_rgb_target;  /* bytes; plane_stride: CHW only */
 aa_status aa_render_rgb_async( aa_ctx * ctx, aa_stream * const * streams, int n, const int * frame_index, int format,
                                const aa_rgb_target * targets, const double mean[3], const double std[3], void * consumer_stream );
+/* Decoded frames scored against originals on the device (BaseRaster::quality, util/raster.cc:63-66 -> util/ssim.cc:57-71: x264's SSIM;
+ * what Encoder::apply_best_loopfilter_settings, encode_with_minimum_ssim and xc-ssim ask of a raster): frame frame_index[i] of
+ * streams[i] against originals[i], plane by plane over the PADDED planes (aa_raster_geometry for Y, half of it each way for U and V),
+ * all n in one pair of kernels on the compute stream behind the decode of those frames.  Frames of different sizes may share a call.
+ *   originals[i]: DEVICE pointers, row strides in bytes >= the plane's width; u, v are ignored for AA_QUALITY_Y.  The other side may be
+ *   a decoded frame too: what aa_stream_raster_device returns, with strides = the padded widths.
+ *   ssim_dev[i * planes + p] (device): the value aa_ssim_host returns for those two planes, bit for bit.
+ *   sse_dev[i * planes + p] (device; NULL: not wanted): the exact sum of squared differences over the padded plane.
+ * Nothing is copied to the host.  consumer_stream as for aa_render_rgb_async: the compute stream waits for it before the kernels and
+ * it waits for them; NULL: the results are valid after aa_ctx_sync.  The frames must have been submitted and not released; one released
+ * right after the call is still scored correctly.  No decoder state, hash or raster changes. */
+enum { AA_QUALITY_Y = 1, AA_QUALITY_YUV = 3 };                       /* number of planes scored */
+typedef struct aa_quality_ref { const void * y, * u, * v; int64_t y_stride, uv_stride; } aa_quality_ref;  /* DEVICE memory, bytes */
+aa_status aa_quality_batch_async( aa_ctx * ctx, aa_stream * const * streams, int n, const int * frame_index,
+                                  const aa_quality_ref * originals, int planes,
+                                  double * ssim_dev, uint64_t * sse_dev, void * consumer_stream );
 /* References::last/golden/alternative after the most recently SUBMITTED frame: frame indices (-1 = initial blank). */
 aa_status aa_stream_references( const aa_stream * s, int * last, int * golden, int * alternate );
 /* Identity of the three reference rasters as they stand now (all frames handed to aa_decode_batch so far applied): equal

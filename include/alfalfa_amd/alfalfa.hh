@@ -28,6 +28,7 @@
 // names into the global namespace (drop-in for code written against the reference headers).
 #pragma once
 
+#include <array>
 #include <cassert>
 #include <cstdint>
 #include <cstdio>
@@ -382,7 +383,48 @@ public:
   }
   bool operator==( const RasterHandle & o ) const { return hash() == o.hash(); }      // raster_handle.cc:184-194: by hash
   bool operator!=( const RasterHandle & o ) const { return !operator==( o ); }
+  // BaseRaster::quality (raster.cc:63-66) of two decoded rasters of one context, computed where they lie: SSIM of the luma planes on
+  // the device, the value VP8Raster::quality gives for their downloads; neither raster comes to the host (quality_batch below)
+  double quality( const RasterHandle & other ) const;
 };
+
+// Extension beside the reference's names: BaseRaster::quality of many pairs of decoded rasters at once, on the device
+// (aa_quality_batch_async) -> per pair the SSIM of Y, U, V over the padded planes (U and V: 0 unless all_planes).  Every raster must
+// come from a decoded frame of a decoder on one context, and the two of a pair must have one size.  Only the scores come back: the
+// kernels write them into pinned host memory, and the call returns when they are there.
+inline std::vector<std::array<double, 3>> quality_batch( const std::vector<RasterHandle> & rasters, const std::vector<RasterHandle> & originals,
+                                                         const bool all_planes = false )
+{
+  if ( rasters.empty() || rasters.size() != originals.size() ) throw LogicError();
+  const std::shared_ptr<GpuContext> & ctx = rasters.front().owner()->ctx;
+  const size_t n = rasters.size();
+  const int planes = all_planes ? AA_QUALITY_YUV : AA_QUALITY_Y;
+  std::vector<aa_stream *> streams;
+  std::vector<int> frames;
+  std::vector<aa_quality_ref> refs( n );
+  for ( size_t i = 0; i < n; i++ ) {
+    const RasterHandle & r = rasters[i], & o = originals[i];
+    if ( r.frame_index() < 0 || o.frame_index() < 0 || r.owner()->ctx != ctx || o.owner()->ctx != ctx ) throw LogicError();
+    if ( r.owner()->width != o.owner()->width || r.owner()->height != o.owner()->height ) throw LogicError();
+    streams.push_back( r.owner()->stream );
+    frames.push_back( r.frame_index() );
+    void * y = nullptr, * u = nullptr, * v = nullptr;
+    check( aa_stream_raster_device( o.owner()->stream, o.frame_index(), &y, &u, &v ) );
+    uint32_t pw = 0, ph = 0;
+    aa_raster_geometry( o.owner()->width, o.owner()->height, &pw, &ph );
+    refs[i].y = y; refs[i].u = u; refs[i].v = v;
+    refs[i].y_stride = pw; refs[i].uv_stride = pw / 2;
+  }
+  struct Pinned { void * p = nullptr; ~Pinned() { aa_pinned_free( p ); } } scores;
+  check( aa_pinned_alloc( ctx->get(), n * planes * sizeof( double ), &scores.p ) );
+  check( aa_quality_batch_async( ctx->get(), streams.data(), static_cast<int>( n ), frames.data(), refs.data(), planes,
+                                 static_cast<double *>( scores.p ), nullptr, nullptr ) );
+  ctx->sync();
+  std::vector<std::array<double, 3>> ret( n, std::array<double, 3> { { 0.0, 0.0, 0.0 } } );
+  for ( size_t i = 0; i < n; i++ ) for ( int p = 0; p < planes; p++ ) ret[i][p] = static_cast<const double *>( scores.p )[i * planes + p];
+  return ret;
+}
+inline double RasterHandle::quality( const RasterHandle & other ) const { return quality_batch( { *this }, { other } ).front()[0]; }
 
 // Extension beside the reference's names (what VideoDisplay::draw's shader does with a shown raster, display.cc): decoded rasters
 // -> RGB in the caller's device buffers, one kernel for the lot (aa_render_rgb_async: formats AA_RGB_*, targets in bytes).  Every

@@ -9,5 +9,6 @@ src=alfalfa_amd/csrc; inc=include
 if [ "$rev" != "-" ]; then
   tmp=$(mktemp -d); git archive "$rev" alfalfa_amd/csrc include | tar -x -C "$tmp"; src=$tmp/alfalfa_amd/csrc; inc=$tmp/include
 fi
+if [ -f $src/quality_kernels.hip ]; then set -- "$@" $src/quality_kernels.hip; fi     # (revisions before the quality kernels have no such file)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -Wno-unused-function "$@" $src/parser.cpp $src/runtime.cpp $src/kernels.hip $src/parse_kernels.hip -o gpurun_in/libs/$name.so
 ls -la gpurun_in/libs/$name.so
