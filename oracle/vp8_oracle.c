@@ -1071,3 +1071,6 @@ void vp8o_stage_filter_edge( uint8_t px[8], int is_mb_edge, int interior_limit, 
 }
 /* the limits NormalLoopFilter derives from a level (loopfilter.cc:81-125): out = interior, mb edge, sub-block edge, hev threshold */
 void vp8o_stage_filter_limits( int level, int sharpness, int key_frame, int out[4] ) { filter_limits( level, sharpness, key_frame, out ); }
+/* chroma vector from the sum of four luma vector components (MotionVector::luma_to_chroma, macroblock.cc:289-299; the sum is
+ * formed in int16 as at macroblock.cc:443-454): exactly what the macroblock-header pass above stores into uv_mv */
+int vp8o_stage_chroma_mv( int sum_of_four ) { return chroma_round( (int16_t) sum_of_four ); }

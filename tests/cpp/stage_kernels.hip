@@ -121,6 +121,13 @@ __global__ void k_lf_edge( int n, const uint8_t * px, const uint8_t * level, con
   lf_edge_pk( P, mb_edge[i] != 0, ~0u, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7] );
   for ( int k = 0; k < 8; k++ ) { out[16 * i + k] = static_cast<uint8_t>( v[k] & 0xFFu ); out[16 * i + 8 + k] = static_cast<uint8_t>( ( v[k] >> 16 ) & 0xFFu ); }
 }
+// ---- chroma vector component from the sum of four luma vector components (chroma_mv: macroblock.cc:289-299) ----
+__global__ void k_chroma_mv( int n, const int * sum, int * out )
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( i >= n ) return;
+  out[i] = chroma_mv( sum[i] );
+}
 
 int blocks_for( int n ) { return ( n + 63 ) / 64; }
 } // namespace
@@ -169,6 +176,12 @@ int stage_lf_edge( int n, const uint8_t * px, const uint8_t * level, const uint8
 {
   DevBuf<uint8_t> p( px, size_t( n ) * 16 ), lv( level, n ), sh( sharp, n ), k( key, n ), mb( mb_edge, n ), o( nullptr, size_t( n ) * 16 );
   hipLaunchKernelGGL( k_lf_edge, dim3( blocks_for( n ) ), dim3( 64 ), 0, nullptr, n, p.p, lv.p, sh.p, k.p, mb.p, o.p );
+  return finish() || !o.back( out );
+}
+int stage_chroma_mv( int n, const int * sum, int * out )
+{
+  DevBuf<int> s( sum, n ), o( nullptr, n );
+  hipLaunchKernelGGL( k_chroma_mv, dim3( blocks_for( n ) ), dim3( 64 ), 0, nullptr, n, s.p, o.p );
   return finish() || !o.back( out );
 }
 

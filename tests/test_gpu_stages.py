@@ -9,6 +9,7 @@ citing the reference lines it follows).  The raster tests say WHICH macroblock d
     the 16x16 / 8x8 intra predictors                           prediction.cc:385-431
     one six-tap pass on packed bytes, all fractions / offsets  prediction.cc:645-653, 861-915
     the normal loop filter, macroblock and sub-block edges     loopfilter_filters.hh:50-183, loopfilter.cc:81-125
+    the chroma vector from a sum of four luma vectors          macroblock.cc:289-299, 443-454  (every reachable sum)
 
 Inputs include the extremes (coefficients and quantisers whose product wraps int16 -- quirk Q4 --, saturating residuals, flat and
 noisy pixel rows)."""
@@ -51,6 +52,7 @@ def stage():
 def ora():
     L = vo.lib()
     L.vp8o_stage_sixtap.restype = C.c_int
+    L.vp8o_stage_chroma_mv.restype = C.c_int; L.vp8o_stage_chroma_mv.argtypes = [C.c_int]
     return L
 
 
@@ -211,3 +213,18 @@ def test_the_loop_filter_edges(stage, ora):
     bad = np.nonzero((got != want).reshape(n, -1).any(axis=1))[0]
     assert len(bad) == 0, "loop filter level %d sharpness %d key %d mb_edge %d px %r: got %r want %r" % (
         level[bad[0]], sharp[bad[0]], key[bad[0]], mb[bad[0]], px[bad[0]], got[bad[0]], want[bad[0]])
+
+
+def test_the_chroma_vector_of_every_four_vector_sum(stage, ora):
+    """chroma_mv over EVERY sum of four vector components, -4 * 2047 * 2 .. +4 * 2047 * 2, odd sums included (a stream's vectors are
+    even, tests/motion_census.py): sum / 8 rounded half away from zero, negative sums too.  The whole-vector path passes 4 * mv, the
+    SPLITMV path the sum of four different vectors.  tests/test_motion_streams.py pins the oracle's wrapper to the uv_mv the
+    whole-frame oracle decodes with."""
+    lim = 4 * 2047 * 2
+    sums = np.arange(-lim, lim + 1, dtype=np.int32)
+    want = np.array([ora.vp8o_stage_chroma_mv(int(s)) for s in sums], np.int32)
+    got = np.zeros_like(sums)
+    assert stage.stage_chroma_mv(len(sums), ptr(sums), ptr(got)) == 0
+    bad = np.nonzero(got != want)[0]
+    assert len(bad) == 0, "chroma_mv: %d of %d sums differ; first: sum %d (mod 8 = %d): got %d want %d" % (
+        len(bad), len(sums), sums[bad[0]], sums[bad[0]] % 8, got[bad[0]], want[bad[0]])
