@@ -142,10 +142,8 @@ int launch_gather_rasters( const aa_gather_job * jobs, int n, uint8_t * staging,
 // jobs[i] -> RGB in `format` (AA_RGB_*), one launch for the lot; table: 3 x 256 output values (float formats); max_threads: the largest
 // job's groups * row pairs
 int launch_render_rgb( const aa_rgb_job * jobs, int n, int format, const uint32_t * table, uint32_t max_threads, void * stream );
-// per-window SSIM terms of two planes (stride = width; width a multiple of 8): (height/4 - 1) x (width/4 - 1) floats
 // dst = src with lf_level := byte `segment_id` of `levels` (records are 80 bytes, 16-byte aligned)
 int launch_lf_relevel( const aa_mb_info * src, aa_mb_info * dst, unsigned nmb, uint32_t levels, void * stream );
-int launch_ssim_windows( const uint8_t * a, const uint8_t * b, int width, int height, float * out, void * stream );
 // quality_kernels.hip: jobs[i] (n_planes of them) -> ssim[i], sse[i] (optional; zeroed by the caller): k_quality_blocks over
 // max_blocks x n_planes workgroups (max_blocks: the largest job's strips * chunks), then k_quality_sum; group_values: the workspace
 int launch_quality( const aa_quality_job * jobs, int n_planes, uint32_t max_blocks, float * group_values, double * ssim, unsigned long long * sse, void * stream );

@@ -1,26 +1,12 @@
-// runtime.cpp, part 9 of 9 (ABI): the encoder's loop-filter level search on the GPU (aa_stream_lf_search, SSIM) and reference access.
+// runtime.cpp, part 9 of 9 (ABI): the encoder's loop-filter level search on the GPU (aa_stream_lf_search; its candidates are scored by
+// quality_of_planes, runtime_quality.inc), x264's SSIM of planes in host memory (aa_ssim_host) and reference access.
 extern "C" {
 namespace {
-// x264's pixel_ssim_wxh over per-window terms (floats, four windows at a time, row by row) / count, for n candidates; then the
-// reference's choice: ascending levels, the first one that does not improve on the best so far ends the search.
-void score_candidates( const std::vector<float> & win, int n, int w4, int h4, int level_lo, int * best_level, double * best_ssim, double * ssim_out )
+// The reference's choice (encoder.cc:489-503): ascending levels, the first one that does not improve on the best so far ends the search.
+void choose_level( const double * q, int n, int level_lo, int * best, double * best_q )
 {
-  const size_t windows = size_t( w4 - 1 ) * ( h4 - 1 );
-  int best = level_lo; double best_q = -1.0; bool searching = true;
-  for ( int i = 0; i < n; i++ ) {
-    float total = 0.0f;
-    for ( int y = 0; y < h4 - 1; y++ )
-      for ( int x = 0; x < w4 - 1; x += 4 ) {
-        float part = 0.0f;
-        for ( int k = x; k < std::min( x + 4, w4 - 1 ); k++ ) part += win[windows * i + size_t( y ) * ( w4 - 1 ) + k];
-        total += part;
-      }
-    const double q = static_cast<double>( total ) / static_cast<double>( windows );
-    if ( ssim_out ) ssim_out[i] = q;
-    if ( searching ) { if ( q > best_q ) { best_q = q; best = level_lo + i; } else searching = false; }
-  }
-  if ( best_level ) *best_level = best;
-  if ( best_ssim ) *best_ssim = best_q;
+  *best = level_lo; *best_q = -1.0;
+  for ( int i = 0; i < n && q[i] > *best_q; i++ ) { *best = level_lo + i; *best_q = q[i]; }
 }
 uint32_t segment_levels( const aa::SegmentationState & seg, int level )      // frame.cc:144-166 + the clamp of macroblock.cc:611-623
 {
@@ -31,11 +17,50 @@ uint32_t segment_levels( const aa::SegmentationState & seg, int level )      // 
   }
   return word;
 }
+
+// What a search holds until it returns: its scratch decoders and device memory, which work queued on the compute stream may still use.
+struct LfScratch {
+  aa_ctx * ctx; std::vector<aa_stream *> streams; uint8_t * dev = nullptr;
+  ~LfScratch() { (void) hipStreamSynchronize( ctx->compute ); for ( aa_stream * c : streams ) if ( c ) aa_stream_destroy( c ); if ( dev ) (void) hipFree( dev ); }
+};
+// A scratch decoder that stands where s stands before this frame: DecoderState and the three references.
+aa_status clone_before_frame( aa_stream * s, aa_stream ** out )
+{
+  if ( aa_status st = aa_stream_create( s->ctx, s->parser.width(), s->parser.height(), out ) ) return st;
+  ( *out )->parser = s->parser;
+  const void * planes[3][3]; const int is_host[3] = { 0, 0, 0 };
+  for ( int r = 0; r < 3; r++ ) for ( int p = 0; p < 3; p++ ) planes[r][p] = slot_plane( s, s->cur_ref_slot[r], p );
+  return aa_stream_set_references( *out, planes, is_host );
+}
+// The end of both routes.  luma: every candidate's padded luma plane, its filtering queued on the compute stream; dev: lf_score_bytes
+// of device memory for the original and the n values.  One quality_of_planes call, n doubles come back, then the choice.
+size_t lf_score_bytes( const aa_stream * s, int n ) { return align_up( s->plane_bytes[0] ) + size_t( n ) * sizeof( double ); }
+aa_status score_and_choose( aa_stream * s, const std::vector<const uint8_t *> & luma, const uint8_t * original_luma, uint8_t * dev,
+                            int level_lo, int * best_level, double * best_ssim, double * ssim_out )
+{
+  aa_ctx * ctx = s->ctx;
+  const int n = static_cast<int>( luma.size() );
+  double * q_dev = reinterpret_cast<double *>( dev + align_up( s->plane_bytes[0] ) );
+  HIP_TRY( hipMemcpyAsync( dev, original_luma, s->plane_bytes[0], hipMemcpyHostToDevice, ctx->compute ) );
+  std::vector<QualityPair> pairs( n );
+  for ( int i = 0; i < n; i++ ) pairs[i] = { luma[i], s->pw, dev, s->pw, static_cast<uint32_t>( s->pw ), static_cast<uint32_t>( s->ph ) };
+  if ( aa_status st = quality_of_planes( ctx, pairs.data(), n, q_dev, nullptr, nullptr ) ) return st;
+  std::vector<double> q( n );
+  HIP_TRY( hipMemcpyAsync( q.data(), q_dev, q.size() * sizeof( double ), hipMemcpyDeviceToHost, ctx->compute ) );
+  HIP_TRY( hipStreamSynchronize( ctx->compute ) );
+  if ( aa_status st = check_watchdog( ctx ) ) return st;
+  int best; double best_q;
+  choose_level( q.data(), n, level_lo, &best, &best_q );
+  if ( best_level ) *best_level = best;
+  if ( best_ssim ) *best_ssim = best_q;
+  if ( ssim_out ) std::copy( q.begin(), q.end(), ssim_out );
+  return AA_OK;
+}
 } // namespace
 
 /* BaseRaster::quality on HOST planes (util/raster.cc:63-66 -> util/ssim.cc:57-71 -> libx264's pixel_ssim_wxh): the same
- * measure aa_stream_lf_search computes on the device, for callers that hold rasters in host memory (VP8Raster::quality in the
- * shim).  Plain host arithmetic -- the reference does this on the CPU too. */
+ * measure k_quality_blocks / k_quality_sum compute on the device (for aa_quality_batch_async and aa_stream_lf_search), for callers
+ * that hold rasters in host memory (VP8Raster::quality in the shim).  Plain host arithmetic -- the reference does this on the CPU too. */
 aa_status aa_ssim_host( const uint8_t * a, const uint8_t * b, int width, int height, double * out )
 {
   if ( !a || !b || !out || width < 8 || height < 8 ) return fail( AA_ERR_ARGUMENT, "aa_ssim_host: null plane or a plane smaller than one 8x8 window" );
@@ -66,34 +91,33 @@ aa_status aa_ssim_host( const uint8_t * a, const uint8_t * b, int width, int hei
       const float den = static_cast<float>( v[0] * v[0] + v[1] * v[1] + c1 ) * static_cast<float>( vars + c2 );
       win[size_t( y ) * ( w4 - 1 ) + x] = num / den;
     }
-  score_candidates( win, 1, w4, h4, 0, nullptr, nullptr, out );
+  // x264's pixel_ssim_wxh: four neighbouring terms left to right into a float, those parts one after another, row after row, into
+  // one float total; the mean in double precision.  The order is part of the value.
+  float total = 0.0f;
+  for ( int y = 0; y < h4 - 1; y++ )
+    for ( int x = 0; x < w4 - 1; x += 4 ) {
+      float part = 0.0f;
+      for ( int k = x; k < std::min( x + 4, w4 - 1 ); k++ ) part += win[size_t( y ) * ( w4 - 1 ) + k];
+      total += part;
+    }
+  *out = static_cast<double>( total ) / static_cast<double>( win.size() );
   return AA_OK;
 }
 
-
+// The search under the diagonal schedule (no row-pipelined filter): every candidate is decoded by a scratch decoder of its own.
 static aa_status lf_search_by_decoders( aa_stream * s, const uint8_t * data, size_t size, const uint8_t * original_luma,
                                         int level_lo, int level_hi, int * best_level, double * best_ssim, double * ssim_out, uint8_t * rasters_out )
 {
-  if ( !s || !data || !original_luma ) return fail( AA_ERR_ARGUMENT, "aa_stream_lf_search: null argument" );
-  if ( level_lo < 0 || level_hi > 63 || level_lo > level_hi ) return fail( AA_ERR_ARGUMENT, "aa_stream_lf_search: levels must be 0 <= lo <= hi <= 63" );
   aa_ctx * ctx = s->ctx;
-  if ( aa_status st = set_device( ctx ) ) return st;
-  if ( s->next_submit != static_cast<int>( s->frames.size() ) ) return fail( AA_ERR_LOGIC, "aa_stream_lf_search: parsed frames are still waiting to be decoded" );
-  if ( aa_status st = segmap_to_host( s ) ) return st;
   const int n = level_hi - level_lo + 1;
-  std::vector<aa_stream *> cand( n, nullptr );
+  LfScratch scratch { ctx, std::vector<aa_stream *>( n, nullptr ) };
+  std::vector<aa_stream *> & cand = scratch.streams;
   std::vector<int> fis( n, -1 );
-  struct Cleanup { std::vector<aa_stream *> & v; uint8_t * orig = nullptr; float * win = nullptr;
-                   ~Cleanup() { for ( aa_stream * c : v ) if ( c ) aa_stream_destroy( c ); if ( orig ) (void) hipFree( orig ); if ( win ) (void) hipFree( win ); } } cleanup { cand };
-  const void * planes[3][3]; const int on_device[3] = { 0, 0, 0 };
-  for ( int r = 0; r < 3; r++ ) for ( int p = 0; p < 3; p++ ) planes[r][p] = slot_plane( s, s->cur_ref_slot[r], p );
   const size_t job_bytes = align_up( sizeof( aa_dev_frame ) );
   for ( int i = 0; i < n; i++ ) {
     const int level = level_lo + i;
-    if ( aa_status st = aa_stream_create( ctx, s->parser.width(), s->parser.height(), &cand[i] ) ) return st;
+    if ( aa_status st = clone_before_frame( s, &cand[i] ) ) return st;
     aa_stream * c = cand[i];
-    c->parser = s->parser;                                               // DecoderState as it stands before this frame
-    if ( aa_status st = aa_stream_set_references( c, planes, on_device ) ) return st;
     if ( aa_status st = aa_stream_parse( c, data, size, &fis[i], nullptr ) ) return st;
     FrameRec & r = c->frames[fis[i]];
     // the candidate's header: this level, adjustments present and zero.  Per macroblock: the segment's level (frame.cc:144-166)
@@ -105,23 +129,10 @@ static aa_status lf_search_by_decoders( aa_stream * s, const uint8_t * data, siz
     r.host_job->loop_filter_level = static_cast<uint8_t>( level );
   }
   if ( aa_status st = aa_decode_batch( ctx, cand.data(), n, fis.data() ) ) return st;
-
-  // quality of every candidate against the original: per-window terms on the device, x264's summation order on the host
-  const int pw = s->pw, ph = s->ph, w4 = pw >> 2, h4 = ph >> 2;
-  const size_t windows = size_t( w4 - 1 ) * ( h4 - 1 );
-  HIP_TRY( hipMalloc( reinterpret_cast<void **>( &cleanup.orig ), s->plane_bytes[0] ) );
-  HIP_TRY( hipMalloc( reinterpret_cast<void **>( &cleanup.win ), windows * n * sizeof( float ) ) );
-  HIP_TRY( hipMemcpyAsync( cleanup.orig, original_luma, s->plane_bytes[0], hipMemcpyHostToDevice, ctx->compute ) );
-  for ( int i = 0; i < n; i++ ) {
-    const FrameRec & r = cand[i]->frames[fis[i]];
-    if ( const int e = aa::launch_ssim_windows( slot_plane( cand[i], r.out_slot, 0 ), cleanup.orig, pw, ph, cleanup.win + windows * i, ctx->compute ) )
-      return hip_fail( static_cast<hipError_t>( e ), "k_ssim_windows" );
-  }
-  std::vector<float> win( windows * n );
-  HIP_TRY( hipMemcpyAsync( win.data(), cleanup.win, win.size() * sizeof( float ), hipMemcpyDeviceToHost, ctx->compute ) );
-  HIP_TRY( hipStreamSynchronize( ctx->compute ) );
-  if ( aa_status st = check_watchdog( ctx ) ) return st;
-  score_candidates( win, n, w4, h4, level_lo, best_level, best_ssim, ssim_out );
+  HIP_TRY( hipMalloc( reinterpret_cast<void **>( &scratch.dev ), lf_score_bytes( s, n ) ) );
+  std::vector<const uint8_t *> luma( n );
+  for ( int i = 0; i < n; i++ ) luma[i] = slot_plane( cand[i], cand[i]->frames[fis[i]].out_slot, 0 );
+  if ( aa_status st = score_and_choose( s, luma, original_luma, scratch.dev, level_lo, best_level, best_ssim, ssim_out ) ) return st;
   if ( rasters_out )
     for ( int i = 0; i < n; i++ ) {
       uint8_t * dst = rasters_out + size_t( i ) * ( s->plane_bytes[0] + 2 * s->plane_bytes[1] );
@@ -136,8 +147,9 @@ static aa_status lf_search_by_decoders( aa_stream * s, const uint8_t * data, siz
  * for the loop filter: a copy of the unfiltered raster, the macroblock records with the candidate's per-segment level and zero
  * mode / reference adjustments (`filter_adjustments.reset( frame.header() )` after the adjustments were zeroed,
  * encoder.cc:464-470) -- ONE k_loopfilter_rows4 launch over all candidates -- scored with BaseRaster::quality = x264's SSIM of
- * the padded luma planes (util/raster.cc:63-66, util/ssim.cc:57-71).  Selection as in the reference: levels in ascending
- * order, the first one that does not improve on the best so far ends the search (encoder.cc:489-503).
+ * the padded luma planes (util/raster.cc:63-66, util/ssim.cc:57-71): all candidates in ONE quality_of_planes call, one double
+ * each comes back.  Selection as in the reference: levels in ascending order, the first one that does not improve on the best so
+ * far ends the search (encoder.cc:489-503).
  * (With the diagonal schedule -- no row-pipelined filter -- every candidate is decoded by a scratch decoder of its own.) */
 aa_status aa_stream_lf_search( aa_stream * s, const uint8_t * data, size_t size, const uint8_t * original_luma,
                                int level_lo, int level_hi, int * best_level, double * best_ssim, double * ssim_out, uint8_t * rasters_out )
@@ -147,19 +159,14 @@ aa_status aa_stream_lf_search( aa_stream * s, const uint8_t * data, size_t size,
   aa_ctx * ctx = s->ctx;
   if ( aa_status st = set_device( ctx ) ) return st;
   if ( s->next_submit != static_cast<int>( s->frames.size() ) ) return fail( AA_ERR_LOGIC, "aa_stream_lf_search: parsed frames are still waiting to be decoded" );
-  if ( ctx->schedule != 0 ) return lf_search_by_decoders( s, data, size, original_luma, level_lo, level_hi, best_level, best_ssim, ssim_out, rasters_out );
   if ( aa_status st = segmap_to_host( s ) ) return st;
+  if ( ctx->schedule != 0 ) return lf_search_by_decoders( s, data, size, original_luma, level_lo, level_hi, best_level, best_ssim, ssim_out, rasters_out );
   const int n = level_hi - level_lo + 1;
 
   // ---- the unfiltered reconstruction, on a scratch decoder ----
-  aa_stream * x = nullptr;
-  struct Cleanup { aa_ctx * ctx; aa_stream *& x; uint8_t * dev = nullptr;
-                   ~Cleanup() { (void) hipStreamSynchronize( ctx->compute ); if ( x ) aa_stream_destroy( x ); if ( dev ) (void) hipFree( dev ); } } cleanup { ctx, x };
-  if ( aa_status st = aa_stream_create( ctx, s->parser.width(), s->parser.height(), &x ) ) return st;
-  x->parser = s->parser;                                                 // DecoderState as it stands before this frame
-  const void * planes[3][3]; const int on_device[3] = { 0, 0, 0 };
-  for ( int r = 0; r < 3; r++ ) for ( int p = 0; p < 3; p++ ) planes[r][p] = slot_plane( s, s->cur_ref_slot[r], p );
-  if ( aa_status st = aa_stream_set_references( x, planes, on_device ) ) return st;
+  LfScratch scratch { ctx, std::vector<aa_stream *>( 1, nullptr ) };
+  if ( aa_status st = clone_before_frame( s, &scratch.streams[0] ) ) return st;
+  aa_stream * x = scratch.streams[0];
   int fx = -1;
   if ( aa_status st = aa_stream_parse( x, data, size, &fx, nullptr ) ) return st;
   {
@@ -173,14 +180,11 @@ aa_status aa_stream_lf_search( aa_stream * s, const uint8_t * data, size_t size,
   const uint8_t * unfiltered = slot_plane( x, rx.out_slot, 0 );
   const size_t raster_bytes = s->plane_bytes[0] + 2 * s->plane_bytes[1];
 
-  // ---- per candidate: raster | macroblock records | job; then the original and the SSIM terms ----
+  // ---- per candidate: raster | macroblock records | job; then the original and the scores ----
   const size_t mb_bytes = align_up( size_t( nmb ) * sizeof( aa_mb_info ) ), job_bytes = align_up( sizeof( aa_dev_frame ) );
   const size_t per = align_up( raster_bytes ) + mb_bytes + job_bytes;
-  const int pw = s->pw, ph = s->ph, w4 = pw >> 2, h4 = ph >> 2;
-  const size_t windows = size_t( w4 - 1 ) * ( h4 - 1 );
-  const size_t orig_off = per * n, win_off = orig_off + align_up( s->plane_bytes[0] );
-  HIP_TRY( hipMalloc( reinterpret_cast<void **>( &cleanup.dev ), win_off + windows * n * sizeof( float ) ) );
-  uint8_t * base = cleanup.dev;
+  HIP_TRY( hipMalloc( reinterpret_cast<void **>( &scratch.dev ), per * n + lf_score_bytes( s, n ) ) );
+  uint8_t * base = scratch.dev;
   std::vector<aa_dev_frame> jobs( n );
   std::vector<std::pair<uint32_t, const aa_dev_frame *>> keyed;
   std::vector<const uint8_t *> luma( n );
@@ -202,16 +206,7 @@ aa_status aa_stream_lf_search( aa_stream * s, const uint8_t * data, size_t size,
     keyed.emplace_back( ( static_cast<uint32_t>( rx.hdr.mb_width ) << 16 ) | rx.hdr.mb_height, job_dev );
   }
   if ( !keyed.empty() ) if ( aa_status st = launch_lf_rows( ctx, keyed, true, rx.hdr.mb_height, rx.hdr.mb_width ) ) return st;
-  uint8_t * orig_dev = base + orig_off;
-  float * win_dev = reinterpret_cast<float *>( base + win_off );
-  HIP_TRY( hipMemcpyAsync( orig_dev, original_luma, s->plane_bytes[0], hipMemcpyHostToDevice, ctx->compute ) );
-  for ( int i = 0; i < n; i++ )
-    if ( const int e = aa::launch_ssim_windows( luma[i], orig_dev, pw, ph, win_dev + windows * i, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_ssim_windows" );
-  std::vector<float> win( windows * n );
-  HIP_TRY( hipMemcpyAsync( win.data(), win_dev, win.size() * sizeof( float ), hipMemcpyDeviceToHost, ctx->compute ) );
-  HIP_TRY( hipStreamSynchronize( ctx->compute ) );
-  if ( aa_status st = check_watchdog( ctx ) ) return st;
-  score_candidates( win, n, w4, h4, level_lo, best_level, best_ssim, ssim_out );
+  if ( aa_status st = score_and_choose( s, luma, original_luma, base + per * n, level_lo, best_level, best_ssim, ssim_out ) ) return st;
   if ( rasters_out )
     for ( int i = 0; i < n; i++ ) HIP_TRY( hipMemcpy( rasters_out + raster_bytes * i, luma[i], raster_bytes, hipMemcpyDeviceToHost ) );
   return AA_OK;

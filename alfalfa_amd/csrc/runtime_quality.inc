@@ -1,12 +1,71 @@
-// runtime.cpp (ABI), between the rasters and the loop-filter search: decoded frames scored against originals on the device
-// (aa_quality_batch_async; kernels in quality_kernels.hip).
+// runtime.cpp (ABI), between the rasters and the loop-filter search: planes scored against originals on the device -- decoded frames
+// (aa_quality_batch_async) and the candidates of the loop-filter search (runtime_lf_search.inc); kernels in quality_kernels.hip.
 extern "C" {
+namespace {
+struct QualityPair { const uint8_t * a; int64_t stride_a; const uint8_t * b; int64_t stride_b; uint32_t w, h; };   // device planes, w x h pixels
 
-/* BaseRaster::quality (util/raster.cc:63-66) and the squared error of n decoded frames against n originals in device memory: one
- * k_quality_blocks launch over every plane of every pair and one k_quality_sum, on the compute stream behind the decode of those
- * frames -- rasters are recycled in compute-stream order, so a frame released right after the call is still read intact.  The job
- * table goes through a ring of pinned buffers into the call's piece of the device pool, which also holds the group values; the
- * piece goes back by the compute-stream route.  Nothing comes to the host. */
+// SSIM (and, with sse_dev, the squared error) of np pairs of planes in device memory: one k_quality_blocks launch over all of them
+// and one k_quality_sum, on the compute stream.  The job table goes through a ring of pinned buffers into the call's piece of the
+// device pool, which also holds the group values; the piece goes back by the compute-stream route.  Nothing comes to the host.
+aa_status quality_of_planes( aa_ctx * ctx, const QualityPair * pairs, int np, double * ssim_dev, uint64_t * sse_dev, hipStream_t consumer )
+{
+  const int bi = ctx->next_quality_buf;
+  aa_ctx::RgbBuf & qb = ctx->quality_bufs[bi];
+  ctx->next_quality_buf = ( ctx->next_quality_buf + 1 ) % aa_ctx::kBindBufs;
+  if ( qb.busy ) { HIP_TRY( hipEventSynchronize( qb.done ) ); qb.busy = false; }
+  const size_t table_bytes = align_up( size_t( np ) * sizeof( aa_quality_job ) );
+  if ( qb.cap < table_bytes ) {
+    if ( qb.host ) (void) hipHostFree( qb.host );
+    qb.host = nullptr; qb.cap = 0;
+    const size_t cap = align_up( std::max<size_t>( 1536, size_t( np ) * 2 ) * sizeof( aa_quality_job ) );
+    HIP_TRY( hipHostMalloc( reinterpret_cast<void **>( &qb.host ), cap, hipHostMallocDefault ) );
+    qb.cap = cap;
+  }
+  for ( hipEvent_t * e : { &qb.done, &qb.before, &qb.after } ) if ( !*e ) HIP_TRY( hipEventCreateWithFlags( e, hipEventDisableTiming ) );
+  aa_quality_job * jobs = reinterpret_cast<aa_quality_job *>( qb.host );
+  uint64_t floats = 0;
+  uint32_t max_blocks = 0;
+  for ( int i = 0; i < np; i++ ) {
+    const QualityPair & p = pairs[i];
+    aa_quality_job & j = jobs[i];
+    j.a = p.a; j.stride_a = p.stride_a;
+    j.b = p.b; j.stride_b = p.stride_b;
+    j.w4 = p.w >> 2; j.h4 = p.h >> 2;
+    j.groups = ( j.w4 - 1 + 3 ) / 4;
+    j.strips = ( j.h4 - 1 + AA_QUALITY_STRIP_ROWS - 1 ) / AA_QUALITY_STRIP_ROWS;
+    j.chunks = ( j.w4 - 1 + AA_QUALITY_CHUNK_WINDOWS - 1 ) / AA_QUALITY_CHUNK_WINDOWS;
+    j.pad = 0;
+    j.out_off = floats;
+    floats += ( uint64_t( j.h4 - 1 ) * j.groups + 3 ) & ~uint64_t( 3 );
+    max_blocks = std::max( max_blocks, j.strips * j.chunks );
+  }
+  const size_t piece_bytes = table_bytes + floats * sizeof( float );
+  uint8_t * piece = nullptr;
+  if ( aa_status st = dev_alloc_compute( ctx, piece_bytes, &piece ) ) return st;
+  // (only the compute stream touches the piece: the next owner's kernels are behind this call's)
+  struct Back { aa_ctx * c; uint8_t * p; size_t b; ~Back() { dev_free_compute( c, p, b ); } } back { ctx, piece, piece_bytes };
+  if ( consumer ) {
+    HIP_TRY( hipEventRecord( qb.before, consumer ) );
+    HIP_TRY( hipStreamWaitEvent( ctx->compute, qb.before, 0 ) );
+  }
+  HIP_TRY( hipMemcpyAsync( piece, qb.host, size_t( np ) * sizeof( aa_quality_job ), hipMemcpyHostToDevice, ctx->compute ) );
+  HIP_TRY( hipEventRecord( qb.done, ctx->compute ) );
+  qb.busy = true;
+  if ( sse_dev ) HIP_TRY( hipMemsetAsync( sse_dev, 0, size_t( np ) * sizeof( uint64_t ), ctx->compute ) );
+  if ( int e = aa::launch_quality( reinterpret_cast<const aa_quality_job *>( piece ), np, max_blocks, reinterpret_cast<float *>( piece + table_bytes ),
+                                   ssim_dev, reinterpret_cast<unsigned long long *>( sse_dev ), ctx->compute ) )
+    return hip_fail( static_cast<hipError_t>( e ), "k_quality_blocks / k_quality_sum" );
+  if ( consumer ) {
+    HIP_TRY( hipEventRecord( qb.after, ctx->compute ) );
+    HIP_TRY( hipStreamWaitEvent( consumer, qb.after, 0 ) );
+  }
+  return AA_OK;
+}
+} // namespace
+
+/* BaseRaster::quality (util/raster.cc:63-66) and the squared error of n decoded frames against n originals in device memory, on the
+ * compute stream behind the decode of those frames -- rasters are recycled in compute-stream order, so a frame released right after
+ * the call is still read intact.  (quality_of_planes does the work.) */
 aa_status aa_quality_batch_async( aa_ctx * ctx, aa_stream * const * streams, int n, const int * frame_index, const aa_quality_ref * originals,
                                   int planes, double * ssim_dev, uint64_t * sse_dev, void * consumer_stream )
 {
@@ -26,65 +85,19 @@ aa_status aa_quality_batch_async( aa_ctx * ctx, aa_stream * const * streams, int
     if ( o.y_stride < int64_t( s->pw ) || ( planes == AA_QUALITY_YUV && o.uv_stride < int64_t( s->pw / 2 ) ) )
       return fail( AA_ERR_ARGUMENT, "aa_quality_batch_async: row stride smaller than the padded plane's width in original " + std::to_string( i ) );
   }
-  const int np = n * planes;
-  const int bi = ctx->next_quality_buf;
-  aa_ctx::RgbBuf & qb = ctx->quality_bufs[bi];
-  ctx->next_quality_buf = ( ctx->next_quality_buf + 1 ) % aa_ctx::kBindBufs;
-  if ( qb.busy ) { HIP_TRY( hipEventSynchronize( qb.done ) ); qb.busy = false; }
-  const size_t table_bytes = align_up( size_t( np ) * sizeof( aa_quality_job ) );
-  if ( qb.cap < table_bytes ) {
-    if ( qb.host ) (void) hipHostFree( qb.host );
-    qb.host = nullptr; qb.cap = 0;
-    const size_t cap = align_up( std::max<size_t>( 1536, size_t( np ) * 2 ) * sizeof( aa_quality_job ) );
-    HIP_TRY( hipHostMalloc( reinterpret_cast<void **>( &qb.host ), cap, hipHostMallocDefault ) );
-    qb.cap = cap;
-  }
-  for ( hipEvent_t * e : { &qb.done, &qb.before, &qb.after } ) if ( !*e ) HIP_TRY( hipEventCreateWithFlags( e, hipEventDisableTiming ) );
-  aa_quality_job * jobs = reinterpret_cast<aa_quality_job *>( qb.host );
-  uint64_t floats = 0;
-  uint32_t max_blocks = 0;
+  std::vector<QualityPair> pairs;
+  pairs.reserve( size_t( n ) * planes );
   for ( int i = 0; i < n; i++ ) {
     aa_stream * s = streams[i];
     const int slot = s->frames[frame_index[i]].out_slot;
     const aa_quality_ref & o = originals[i];
     const void * ob[3] = { o.y, o.u, o.v };
     for ( int p = 0; p < planes; p++ ) {
-      aa_quality_job & j = jobs[i * planes + p];
       const uint32_t w = p ? s->pw / 2 : s->pw, h = p ? s->ph / 2 : s->ph;        // (multiples of 16 / 8: at least one window each way)
-      j.a = slot_plane( s, slot, p ); j.stride_a = w;
-      j.b = static_cast<const uint8_t *>( ob[p] ); j.stride_b = p ? o.uv_stride : o.y_stride;
-      j.w4 = w >> 2; j.h4 = h >> 2;
-      j.groups = ( j.w4 - 1 + 3 ) / 4;
-      j.strips = ( j.h4 - 1 + AA_QUALITY_STRIP_ROWS - 1 ) / AA_QUALITY_STRIP_ROWS;
-      j.chunks = ( j.w4 - 1 + AA_QUALITY_CHUNK_WINDOWS - 1 ) / AA_QUALITY_CHUNK_WINDOWS;
-      j.pad = 0;
-      j.out_off = floats;
-      floats += ( uint64_t( j.h4 - 1 ) * j.groups + 3 ) & ~uint64_t( 3 );
-      max_blocks = std::max( max_blocks, j.strips * j.chunks );
+      pairs.push_back( { slot_plane( s, slot, p ), w, static_cast<const uint8_t *>( ob[p] ), p ? o.uv_stride : o.y_stride, w, h } );
     }
   }
-  const size_t piece_bytes = table_bytes + floats * sizeof( float );
-  uint8_t * piece = nullptr;
-  if ( aa_status st = dev_alloc_compute( ctx, piece_bytes, &piece ) ) return st;
-  // (only the compute stream touches the piece: the next owner's kernels are behind this call's)
-  struct Back { aa_ctx * c; uint8_t * p; size_t b; ~Back() { dev_free_compute( c, p, b ); } } back { ctx, piece, piece_bytes };
-  const hipStream_t consumer = static_cast<hipStream_t>( consumer_stream );
-  if ( consumer ) {
-    HIP_TRY( hipEventRecord( qb.before, consumer ) );
-    HIP_TRY( hipStreamWaitEvent( ctx->compute, qb.before, 0 ) );
-  }
-  HIP_TRY( hipMemcpyAsync( piece, qb.host, size_t( np ) * sizeof( aa_quality_job ), hipMemcpyHostToDevice, ctx->compute ) );
-  HIP_TRY( hipEventRecord( qb.done, ctx->compute ) );
-  qb.busy = true;
-  if ( sse_dev ) HIP_TRY( hipMemsetAsync( sse_dev, 0, size_t( np ) * sizeof( uint64_t ), ctx->compute ) );
-  if ( int e = aa::launch_quality( reinterpret_cast<const aa_quality_job *>( piece ), np, max_blocks, reinterpret_cast<float *>( piece + table_bytes ),
-                                   ssim_dev, reinterpret_cast<unsigned long long *>( sse_dev ), ctx->compute ) )
-    return hip_fail( static_cast<hipError_t>( e ), "k_quality_blocks / k_quality_sum" );
-  if ( consumer ) {
-    HIP_TRY( hipEventRecord( qb.after, ctx->compute ) );
-    HIP_TRY( hipStreamWaitEvent( consumer, qb.after, 0 ) );
-  }
-  return AA_OK;
+  return quality_of_planes( ctx, pairs.data(), n * planes, ssim_dev, sse_dev, static_cast<hipStream_t>( consumer_stream ) );
 }
 
 } // extern "C"

@@ -55,8 +55,8 @@ def test_oracle_ssim_orders_distortions():
 
 
 def test_product_host_ssim_equals_the_oracle():
-    """aa_ssim_host (VP8Raster::quality of the shim; the summation half is shared with aa_stream_lf_search) against the
-    oracle's restatement, bit for bit."""
+    """aa_ssim_host (VP8Raster::quality of the shim; the host's statement of what the quality kernels compute for
+    aa_quality_batch_async and aa_stream_lf_search) against the oracle's restatement, bit for bit."""
     import ctypes as C
     from alfalfa_amd import capi
     L = capi.lib()
