@@ -144,6 +144,9 @@ SYMBOLS = [
     ("aa_stream_raster_hash", C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     ("aa_stream_decoder_hash", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("aa_stream_minihash", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("aa_hash_rasters_async", C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("aa_hash_decoders_async", C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    ("aa_ctx_hash_wait", C.c_int, [_P]), ("aa_ctx_hash_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]), ("aa_ctx_hash_stream", _P, [_P]),
     ("aa_stream_release_frame", C.c_int, [_P, C.c_int]),
     ("aa_stream_set_references", C.c_int, [_P, C.POINTER(_P * 3), C.POINTER(C.c_int)]),
     ("aa_stream_reference_device", C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),

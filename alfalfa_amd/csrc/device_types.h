@@ -144,6 +144,10 @@ int launch_gather_rasters( const aa_gather_job * jobs, int n, uint8_t * staging,
 int launch_render_rgb( const aa_rgb_job * jobs, int n, int format, const uint32_t * table, uint32_t max_threads, void * stream );
 // dst = src with lf_level := byte `segment_id` of `levels` (records are 80 bytes, 16-byte aligned)
 int launch_lf_relevel( const aa_mb_info * src, aa_mb_info * dst, unsigned nmb, uint32_t levels, void * stream );
+// hash_kernels.hip: job i (hash_chain.hh; n of them, longest first) is walked by lane i % lanes_per_wave of wave i / lanes_per_wave; its
+// result goes to results[job.out_index] (out_index < n)
+struct HashJob;
+int launch_hash_chains( const HashJob * jobs, int n, int lanes_per_wave, uint64_t * results, void * stream );
 // quality_kernels.hip: jobs[i] (n_planes of them) -> ssim[i], sse[i] (optional; zeroed by the caller): k_quality_blocks over
 // max_blocks x n_planes workgroups (max_blocks: the largest job's strips * chunks), then k_quality_sum; group_values: the workspace
 int launch_quality( const aa_quality_job * jobs, int n_planes, uint32_t max_blocks, float * group_values, double * ssim, unsigned long long * sse, void * stream );

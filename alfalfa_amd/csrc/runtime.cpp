@@ -40,8 +40,9 @@
 #include "parser.hh"
 #include "tok_fsm.hh"
 #include "coeff_pack.hh"
+#include "hash_chain.hh"
 
-// ONE translation unit, ten source files (round 6; the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
+// ONE translation unit, eleven source files (round 6; the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
 // the pieces share file-local state (the anonymous-namespace helpers, g_last_error) and are #included in dependency order.
 #include "runtime_types.inc"
 #include "runtime_pool.inc"
@@ -51,5 +52,6 @@
 #include "runtime_submit.inc"
 #include "runtime_decode.inc"
 #include "runtime_rasters.inc"
+#include "runtime_hashes.inc"
 #include "runtime_quality.inc"
 #include "runtime_lf_search.inc"

@@ -194,6 +194,8 @@ static void ctx_free( aa_ctx * ctx );
 void aa_ctx_destroy( aa_ctx * ctx )
 {
   if ( !ctx ) return;
+  (void) hipSetDevice( ctx->device );
+  hash_drain( ctx );                    // (outstanding hash calls write the caller's arrays at their wait: not after the handle is gone)
   if ( --ctx->refs == 0 ) ctx_free( ctx );
 }
 static void ctx_free( aa_ctx * ctx )
@@ -217,6 +219,7 @@ static void ctx_free( aa_ctx * ctx )
     if ( rb.dev ) (void) hipFree( rb.dev );
     for ( hipEvent_t e : { rb.done, rb.before, rb.after } ) if ( e ) (void) hipEventDestroy( e );
   }
+  hash_free( ctx );
   for ( auto & qb : ctx->quality_bufs ) {
     if ( qb.host ) (void) hipHostFree( qb.host );
     for ( hipEvent_t e : { qb.done, qb.before, qb.after } ) if ( e ) (void) hipEventDestroy( e );
@@ -447,6 +450,7 @@ void aa_stream_destroy( aa_stream * s )
   if ( !s ) return;
   aa_ctx * ctx = s->ctx;
   (void) hipSetDevice( ctx->device );
+  hash_drain( ctx );                    // (an outstanding hash call may hold this stream's rasters and fills its Slot caches at the wait)
   // Nothing here waits for the reconstruction stream: what queued kernels may still read or write (rasters, records) goes back
   // to the pools through a release epoch, like everything released while the pipeline runs -- a caller that drops a decoder
   // per chunk does not stall.  What IS waited for: uploads out of this stream's pinned staging (it is handed to other parses),

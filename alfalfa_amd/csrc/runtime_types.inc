@@ -183,6 +183,26 @@ struct aa_ctx {
   // the job table of a scoring call (aa_quality_batch_async): written to `host`, copied into the call's pool piece (`dev` stays null)
   RgbBuf quality_bufs[kBindBufs];
   int next_quality_buf = 0;
+  // batched hashes (runtime_hashes.inc): a stream of their own, a ring of pinned buffers (result table, job table, segment maps: read
+  // and written by k_hash_chains over the bus) and the calls whose results nobody has committed yet, oldest first
+  struct Hash {
+    struct Buf { uint8_t * host = nullptr, * dev = nullptr; size_t cap = 0; hipEvent_t ready = nullptr, done = nullptr; };
+    struct Value { uint64_t value = 0; int result = -1; };      // result >= 0: word `result` of the call's result table, else `value`
+    struct Fill { aa_stream * s; int slot; int result; };        // a raster the call holds; result >= 0: its Slot cache is filled at the wait
+    struct Decoder { uint64_t state = 0; int map_result = -1; bool filter = false; uint64_t filter_hash = 0; Value refs[3]; };
+    struct Call {
+      int buf = -1; bool launched = false;
+      std::vector<Fill> held;
+      std::vector<Value> rasters; uint64_t * out = nullptr;                                   // aa_hash_rasters_async
+      std::vector<Decoder> decoders; uint64_t * parts = nullptr, * whole = nullptr; uint32_t * minihash = nullptr;   // aa_hash_decoders_async
+    };
+    std::mutex mu;
+    hipStream_t st = nullptr;
+    Buf bufs[kBindBufs];
+    int next_buf = 0, simds = 0;
+    std::deque<Call> calls;
+    uint64_t stats[4] = { 0, 0, 0, 0 };      // chains launched, bytes walked, rasters answered from the cache, cache entries filled
+  } hash;
   int row_handoff_by_kernel[2] = { 0, 0 };   // (diagnostics: waits the second look ended, k_recon_intra4 / k_loopfilter_rows4)
   std::deque<int> downloads_in_flight;   // gather_bufs whose copy (aa_download_batch_async) nobody has waited for yet, oldest first
   // A parse batch holds its stream for as long as its longest chain (seconds for a key frame): a batch queued behind another
@@ -329,6 +349,7 @@ struct aa_ctx {
 };
 
 namespace { void host_lanes_start( aa_ctx * ctx ); void host_lanes_stop( aa_ctx * ctx ); double host_lanes_rate( aa_ctx * ctx ); }
+namespace { void hash_drain( aa_ctx * ctx ); void hash_free( aa_ctx * ctx ); }      // runtime_hashes.inc
 
 struct aa_stream {
   aa_ctx * ctx;

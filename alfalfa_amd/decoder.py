@@ -100,6 +100,7 @@ class Context:
         self.h = C.c_void_p()
         capi.check(self.L.aa_ctx_create(device, C.byref(self.h)))
         self.device = device
+        self._hash_keep = []                 # host arrays of outstanding hash calls
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -354,11 +355,81 @@ class Context:
             cur.wait_stream(compute)
         return Quality(ssim, sse)
 
+    def _hash_streams(self, what, decoders):
+        n = len(decoders)
+        if n == 0:
+            raise ValueError("%s: need at least one decoder" % what)
+        for i, d in enumerate(decoders):
+            if d.ctx is not self:
+                raise ValueError("%s: decoders[%d] is a decoder of another context" % (what, i))
+        return n, (C.c_void_p * n)(*[d.h for d in decoders])
+
+    def raster_hashes(self, decoders, frame_indices, wait=True):
+        """BaseRaster::raw_hash of frame frame_indices[i] of decoders[i] (aa_hash_rasters_async): what Decoder.raster_hash gives, for
+        all of them by one kernel -- a GPU lane per raster -- without a download.  -> [int]; wait=False: a HashResult whose .result()
+        waits.  The frames may be released right after the call."""
+        n, arr = self._hash_streams("raster_hashes", decoders)
+        if len(frame_indices) != n:
+            raise ValueError("raster_hashes: need as many frame indices as decoders")
+        out = (C.c_uint64 * n)()
+        capi.check(self.L.aa_hash_rasters_async(self.h, arr, n, (C.c_int * n)(*frame_indices), out))
+        r = HashResult(self, (out,), lambda: list(out))
+        return r.result() if wait else r
+
+    def decoder_hashes(self, decoders, wait=True):
+        """DecoderHash of every decoder (aa_hash_decoders_async) -> [([state, last, golden, alternative], hash of the four)], what
+        Decoder.decoder_hash gives; afterwards decoder_hash / minihash / raster_hash of these decoders answer from the cache."""
+        n, arr = self._hash_streams("decoder_hashes", decoders)
+        parts, whole = (C.c_uint64 * (4 * n))(), (C.c_uint64 * n)()
+        capi.check(self.L.aa_hash_decoders_async(self.h, arr, n, parts, whole, None))
+        r = HashResult(self, (parts, whole), lambda: [(list(parts[4 * i:4 * i + 4]), whole[i]) for i in range(n)])
+        return r.result() if wait else r
+
+    def minihashes(self, decoders, wait=True):
+        """Decoder::minihash of every decoder (the low 32 bits of the DecoderHash's hash) -> [int]."""
+        n, arr = self._hash_streams("minihashes", decoders)
+        mini = (C.c_uint32 * n)()
+        capi.check(self.L.aa_hash_decoders_async(self.h, arr, n, None, None, mini))
+        r = HashResult(self, (mini,), lambda: list(mini))
+        return r.result() if wait else r
+
+    def hash_wait(self):
+        """aa_ctx_hash_wait: every outstanding hash call is committed (arrays written, raster caches filled, rasters let go)."""
+        try:
+            capi.check(self.L.aa_ctx_hash_wait(self.h))
+        finally:
+            del self._hash_keep[:]
+
+    def hash_stats(self, reset=False):
+        """-> {"chains", "bytes", "cache_hits", "cache_fills"}: chains launched, bytes walked, rasters answered from the cache, cache
+        entries filled (aa_ctx_hash_stats)."""
+        out = (C.c_uint64 * 4)()
+        capi.check(self.L.aa_ctx_hash_stats(self.h, out, int(reset)))
+        return dict(zip(("chains", "bytes", "cache_hits", "cache_fills"), out))
+
+    def hash_stream(self):
+        return self.L.aa_ctx_hash_stream(self.h)
+
     def decode_batch(self, decoders, frame_indices):
         n = len(decoders)
         arr = (C.c_void_p * n)(*[d.h for d in decoders])
         idx = (C.c_int * n)(*frame_indices)
         capi.check(self.L.aa_decode_batch(self.h, arr, n, idx))
+
+
+class HashResult:
+    """An outstanding hash call (Context.raster_hashes / decoder_hashes / minihashes with wait=False): result() waits (for every
+    outstanding call of the context) and returns the values."""
+
+    def __init__(self, ctx, arrays, read):
+        self.ctx, self._read, self._value = ctx, read, None
+        ctx._hash_keep.append(arrays)        # (the runtime writes into them at the wait: the context holds them until then)
+
+    def result(self):
+        if self._read is not None:
+            self.ctx.hash_wait()
+            self._value, self._read = self._read(), None
+        return self._value
 
 
 class Decoder:

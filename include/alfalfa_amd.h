@@ -420,6 +420,30 @@ aa_status aa_stream_state_hash( aa_stream * s, uint64_t * out );
 aa_status aa_stream_raster_hash( aa_stream * s, int frame_index, uint64_t * out );
 aa_status aa_stream_decoder_hash( aa_stream * s, uint64_t parts[4], uint64_t * whole );
 aa_status aa_stream_minihash( aa_stream * s, uint32_t * out );
+/* The same hashes for MANY rasters / decoders in one call, without a download: every raster whose hash is not cached yet is one chain
+ * of ONE kernel (k_hash_chains: a lane per chain -- the recurrence cannot be split, but chains are independent), on a stream of the
+ * context's own that waits for what the compute stream holds at the call; rasters are deduplicated by device pointer (golden is
+ * often the raster last is; fresh decoders share the context's blank raster).  The segment map of a decoder with segmentation on is
+ * a chain too, of every call (maps change with every frame and have no cache); probability tables and adjustments are hashed on the
+ * host in the call.  A lone 1080p chain takes tens of
+ * milliseconds -- longer than the per-stream route -- and 1 440 of them take as long as one: for a handful of rasters use the
+ * per-stream calls, for a chunk boundary of hundreds of decoders these.
+ *   aa_hash_rasters_async   out[i] = aa_stream_raster_hash( streams[i], frame_index[i] ); same preconditions and errors.
+ *   aa_hash_decoders_async  parts[4 i ..] / whole[i] / minihash[i] = aa_stream_decoder_hash / aa_stream_minihash of streams[i]
+ *                           (any of the three may be NULL); everything parsed must have been submitted.
+ *   aa_ctx_hash_wait        every outstanding call: the host arrays are written (they must live until then), and the per-raster
+ *                           caches filled, so that the per-stream calls above answer without a download.  Waits for the hash stream,
+ *                           not for the compute stream.  aa_ctx_sync does NOT commit hash calls.
+ *   aa_ctx_hash_stats       out[0..3] = chains launched, bytes walked, rasters answered from the cache, cache entries filled.
+ *   aa_ctx_hash_stream      the hipStream_t the kernels run on (for timing with events).
+ * Every raster of a call is held from the call to the wait: a frame released right after the call is still hashed correctly and its
+ * raster goes back to the pool at the wait.  At most 16 calls are outstanding; a seventeenth first commits the oldest.
+ * aa_ctx_destroy and aa_stream_destroy commit outstanding calls first. */
+aa_status aa_hash_rasters_async( aa_ctx * ctx, aa_stream * const * streams, int n, const int * frame_index, uint64_t * out );
+aa_status aa_hash_decoders_async( aa_ctx * ctx, aa_stream * const * streams, int n, uint64_t * parts, uint64_t * whole, uint32_t * minihash );
+aa_status aa_ctx_hash_wait( aa_ctx * ctx );
+aa_status aa_ctx_hash_stats( aa_ctx * ctx, uint64_t out[4], int reset );
+void * aa_ctx_hash_stream( aa_ctx * ctx );
 /* Give back ONE frame: its raster handle (the raster lives on while a reference points at it) and, once decoded, its
  * parsed records -- what the destructor of the last RasterHandle of a frame does in the reference (raster_handle.cc:113-122). */
 aa_status aa_stream_release_frame( aa_stream * s, int frame_index );

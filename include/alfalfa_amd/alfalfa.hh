@@ -912,6 +912,20 @@ public:
     check( aa_stream_decoder_hash( owner_->stream, parts, nullptr ) );
     return DecoderHash( parts[0], parts[1], parts[2], parts[3] );
   }
+  // (not in the reference) The hashes of MANY decoders by one kernel -- a GPU lane per raster and segment map, nothing downloaded
+  // (aa_hash_decoders_async + aa_ctx_hash_wait): afterwards get_hash(), minihash(), minihash_match() of these decoders and
+  // RasterHandle::operator== on their references answer from the per-raster caches.  What a chunk boundary with hundreds of decoders
+  // calls first; for a handful the per-decoder route is faster (a lone 1080p chain takes a lane tens of milliseconds).
+  // All decoders must live on the same GpuContext.
+  static void prefetch_hashes( const std::vector<Decoder *> & decoders )
+  {
+    if ( decoders.empty() ) return;
+    std::vector<aa_stream *> streams( decoders.size() );
+    for ( size_t i = 0; i < decoders.size(); i++ ) streams[i] = decoders[i]->owner_->stream;
+    aa_ctx * const ctx = decoders[0]->owner_->ctx->get();
+    check( aa_hash_decoders_async( ctx, streams.data(), static_cast<int>( streams.size() ), nullptr, nullptr, nullptr ) );
+    check( aa_ctx_hash_wait( ctx ) );
+  }
   uint32_t minihash() const { return static_cast<uint32_t>( get_hash().hash() ); }                  // decoder.cc:516-519
   bool minihash_match( const uint32_t other_minihash ) const { return other_minihash == 0 || minihash() == other_minihash; }   // :522-529
   bool operator==( const Decoder & o ) const { return get_state() == o.get_state() && get_references() == o.get_references(); }   // decoder.cc:155-158
