@@ -1,4 +1,4 @@
-// runtime.cpp, part 5 of 9 (ABI): errors, the host parser's entry points, contexts (create / destroy / info / limits / switches), streams.
+// runtime.cpp, one of its pieces (ABI): errors, the host parser's entry points, contexts (create / destroy / info / limits / switches), streams.
 
 extern "C" {
 
@@ -212,18 +212,10 @@ static void ctx_free( aa_ctx * ctx )
   for ( auto e : ctx->free_events ) (void) hipEventDestroy( e );
   (void) hipEventDestroy( ctx->upload_done );
   if ( ctx->last_raster_download ) (void) hipEventDestroy( ctx->last_raster_download );
-  for ( auto & bb : ctx->bind_bufs ) { if ( bb.host ) (void) hipHostFree( bb.host ); if ( bb.done ) (void) hipEventDestroy( bb.done ); }
-  for ( auto & gb : ctx->gather_bufs ) { if ( gb.host ) (void) hipHostFree( gb.host ); if ( gb.done ) (void) hipEventDestroy( gb.done ); if ( gb.copied ) (void) hipEventDestroy( gb.copied ); }
-  for ( auto & rb : ctx->rgb_bufs ) {
-    if ( rb.host ) (void) hipHostFree( rb.host );
-    if ( rb.dev ) (void) hipFree( rb.dev );
-    for ( hipEvent_t e : { rb.done, rb.before, rb.after } ) if ( e ) (void) hipEventDestroy( e );
-  }
   hash_free( ctx );
-  for ( auto & qb : ctx->quality_bufs ) {
-    if ( qb.host ) (void) hipHostFree( qb.host );
-    for ( hipEvent_t e : { qb.done, qb.before, qb.after } ) if ( e ) (void) hipEventDestroy( e );
-  }
+  for ( JobRing * r : { &ctx->bind_ring, &ctx->gather_ring, &ctx->rgb_ring, &ctx->quality_ring } ) r->destroy();
+  for ( hipEvent_t e : ctx->gather_copied ) if ( e ) (void) hipEventDestroy( e );
+  for ( hipEvent_t e : { ctx->rgb_consumer_ev, ctx->quality_consumer_ev } ) if ( e ) (void) hipEventDestroy( e );
   if ( ctx->ws ) (void) hipFree( ctx->ws );
   if ( ctx->boundary ) (void) hipFree( ctx->boundary );
   tok_free( ctx );

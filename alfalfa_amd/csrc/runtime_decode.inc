@@ -1,4 +1,4 @@
-// runtime.cpp, part 7 of 9 (ABI): frames going to reconstruction -- parse summaries, aa_stream_read_records, the row kernels' launches,
+// runtime.cpp, one of its pieces (ABI): frames going to reconstruction -- parse summaries, aa_stream_read_records, the row kernels' launches,
 // aa_decode_batch, release / rewind.
 extern "C" {
 

@@ -11,25 +11,16 @@ aa_status hash_stream( aa_ctx * ctx )
   return AA_OK;
 }
 
-// what the call needs of the ring: its buffer, free (a call that still owns it -- the sixteenth before this one -- is committed first)
+// what the call needs of the ring: its entry, free (a call that still owns it -- the sixteenth before this one -- is committed first:
+// the results are read out of the entry's host memory at the commit, so `done` alone does not free it)
 aa_status hash_commit_oldest( aa_ctx * ctx );
 aa_status hash_take_buf( aa_ctx * ctx, size_t bytes, int * out )
 {
   aa_ctx::Hash & H = ctx->hash;
-  while ( static_cast<int>( H.calls.size() ) >= aa_ctx::kBindBufs ) if ( aa_status st = hash_commit_oldest( ctx ) ) return st;
-  const int bi = H.next_buf;
-  H.next_buf = ( H.next_buf + 1 ) % aa_ctx::kBindBufs;
-  aa_ctx::Hash::Buf & b = H.bufs[bi];
-  if ( b.cap < bytes ) {
-    if ( b.host ) (void) hipHostFree( b.host );
-    b.host = b.dev = nullptr; b.cap = 0;
-    const size_t cap = align_up( std::max<size_t>( bytes * 2, size_t( 64 ) << 10 ) );
-    HIP_TRY( hipHostMalloc( reinterpret_cast<void **>( &b.host ), cap, hipHostMallocDefault ) );
-    HIP_TRY( hipHostGetDevicePointer( reinterpret_cast<void **>( &b.dev ), b.host, 0 ) );
-    b.cap = cap;
-  }
-  for ( hipEvent_t * e : { &b.ready, &b.done } ) if ( !*e ) HIP_TRY( hipEventCreateWithFlags( e, hipEventDisableTiming ) );
-  *out = bi;
+  while ( static_cast<int>( H.calls.size() ) >= kBindBufs ) if ( aa_status st = hash_commit_oldest( ctx ) ) return st;
+  JobRing::Entry * b = nullptr;
+  if ( aa_status st = H.ring.take( bytes, size_t( 64 ) << 10, &b, out ) ) return st;
+  if ( !H.ready[*out] ) HIP_TRY( hipEventCreateWithFlags( &H.ready[*out], hipEventDisableTiming ) );
   return AA_OK;
 }
 
@@ -98,7 +89,7 @@ aa_status hash_launch( aa_ctx * ctx, HashPlan & plan, aa_ctx::Hash::Call & call 
     }
     const size_t jobs_off = align_up( n * sizeof( uint64_t ) ), maps_off = jobs_off + align_up( n * sizeof( aa::HashJob ) );
     if ( aa_status st = hash_take_buf( ctx, maps_off + plan.maps.size(), &call.buf ) ) return st;
-    aa_ctx::Hash::Buf & b = H.bufs[call.buf];
+    JobRing::Entry & b = H.ring.entries[call.buf];
     std::memset( b.host, 0, n * sizeof( uint64_t ) );
     if ( !plan.maps.empty() ) std::memcpy( b.host + maps_off, plan.maps.data(), plan.maps.size() );
     // longest chains first: the lanes of a wave get neighbours of the sorted table and finish together
@@ -117,16 +108,16 @@ aa_status hash_launch( aa_ctx * ctx, HashPlan & plan, aa_ctx::Hash::Call & call 
     const int lanes_per_wave = static_cast<int>( std::min<size_t>( 64, ( n + H.simds - 1 ) / H.simds ) );
     // behind everything the compute stream holds now: the frames are decoded by then.  Never IN the compute stream: a chain of a
     // 1080p raster runs for tens of milliseconds
-    HIP_TRY( hipEventRecord( b.ready, ctx->compute ) );
-    HIP_TRY( hipStreamWaitEvent( H.st, b.ready, 0 ) );
+    HIP_TRY( hipEventRecord( H.ready[call.buf], ctx->compute ) );
+    HIP_TRY( hipStreamWaitEvent( H.st, H.ready[call.buf], 0 ) );
     if ( int e = aa::launch_hash_chains( reinterpret_cast<const aa::HashJob *>( b.dev + jobs_off ), static_cast<int>( n ), lanes_per_wave,
                                          reinterpret_cast<uint64_t *>( b.dev ), H.st ) )
       return hip_fail( static_cast<hipError_t>( e ), "k_hash_chains" );
     call.launched = true;
-    HIP_TRY( hipEventRecord( b.done, H.st ) );
+    if ( aa_status st = H.ring.mark( b, H.st ) ) return st;
     H.stats[0] += n; H.stats[1] += steps;
   } else {
-    while ( static_cast<int>( H.calls.size() ) >= aa_ctx::kBindBufs ) if ( aa_status st = hash_commit_oldest( ctx ) ) return st;
+    while ( static_cast<int>( H.calls.size() ) >= kBindBufs ) if ( aa_status st = hash_commit_oldest( ctx ) ) return st;
   }
   H.calls.push_back( std::move( call ) );
   return AA_OK;
@@ -142,9 +133,9 @@ aa_status hash_commit_oldest( aa_ctx * ctx )
   struct Held { aa_ctx::Hash::Call & c; ~Held() { hash_release_held( c ); } } held { call };
   const uint64_t * results = nullptr;
   if ( call.launched ) {
-    HIP_TRY( hipEventSynchronize( H.bufs[call.buf].done ) );
+    HIP_TRY( hipEventSynchronize( H.ring.entries[call.buf].done ) );
     if ( aa_status st = check_watchdog( ctx ) ) return st;
-    results = reinterpret_cast<const uint64_t *>( H.bufs[call.buf].host );
+    results = reinterpret_cast<const uint64_t *>( H.ring.entries[call.buf].host );
   }
   const auto value = [&]( const aa_ctx::Hash::Value & v ) { return v.result >= 0 ? results[v.result] : v.value; };
   for ( auto & f : call.held ) {
@@ -178,11 +169,8 @@ void hash_free( aa_ctx * ctx )
 {
   aa_ctx::Hash & H = ctx->hash;
   if ( H.st ) { (void) hipStreamSynchronize( H.st ); (void) hipStreamDestroy( H.st ); H.st = nullptr; }
-  for ( auto & b : H.bufs ) {
-    if ( b.host ) (void) hipHostFree( b.host );
-    for ( hipEvent_t e : { b.ready, b.done } ) if ( e ) (void) hipEventDestroy( e );
-    b = aa_ctx::Hash::Buf();
-  }
+  H.ring.destroy();
+  for ( hipEvent_t & e : H.ready ) if ( e ) { (void) hipEventDestroy( e ); e = nullptr; }
 }
 
 } // namespace
@@ -196,15 +184,8 @@ aa_status aa_hash_rasters_async( aa_ctx * ctx, aa_stream * const * streams, int 
 {
   if ( !ctx || !streams || !frame_index || !out || n <= 0 ) return fail( AA_ERR_ARGUMENT, "aa_hash_rasters_async: bad argument" );
   if ( aa_status st = set_device( ctx ) ) return st;
-  for ( int i = 0; i < n; i++ ) {
-    const aa_stream * s = streams[i];
-    if ( !s || s->ctx != ctx ) return fail( AA_ERR_ARGUMENT, "aa_hash_rasters_async: stream belongs to another context" );
-    const int fi = frame_index[i];
-    if ( fi < 0 || fi >= static_cast<int>( s->frames.size() ) ) return fail( AA_ERR_ARGUMENT, "aa_hash_rasters_async: bad argument" );
-    const FrameRec & r = s->frames[fi];
-    if ( fi >= s->next_submit || !r.placed ) return fail( AA_ERR_LOGIC, "aa_hash_rasters_async: frame not decoded yet" );
-    if ( !r.handle_held ) return fail( AA_ERR_LOGIC, "aa_hash_rasters_async: frame was released" );
-  }
+  for ( int i = 0; i < n; i++ )
+    if ( aa_status st = held_decoded_frame( "aa_hash_rasters_async", ctx, streams[i], frame_index[i], nullptr ) ) return st;
   std::lock_guard<std::mutex> g( ctx->hash.mu );
   HashPlan plan;
   aa_ctx::Hash::Call call;
@@ -239,26 +220,21 @@ aa_status aa_hash_decoders_async( aa_ctx * ctx, aa_stream * const * streams, int
     aa_stream * s = streams[i];
     const aa::Parser & ps = s->parser;
     aa_ctx::Hash::Decoder & d = call.decoders[i];
-    // DecoderState::hash as state_hash (runtime_rasters.inc) forms it, up to the segment map
-    const aa::ProbTables & t = ps.probs();
-    uint64_t ph = 0;
-    hrange_u8( ph, &t.coeff[0][0][0][0], 1056 ); hrange_u8( ph, t.y_mode, 4 ); hrange_u8( ph, t.uv_mode, 3 ); hrange_u8( ph, &t.mv[0][0], 38 );
-    hcombine( d.state, ps.width() ); hcombine( d.state, ps.height() ); hcombine( d.state, ph );
+    // DecoderState::hash as state_hash (runtime_rasters.inc) forms it; the walk over the segment map is a chain of the kernel
+    StateHashParts sp;
+    state_hash_parts( ps, sp );
+    d.state = sp.head;
     const aa::SegmentationState & sg = ps.segmentation();
     if ( sg.enabled ) {
-      uint64_t sh = 0;
-      hcombine( sh, sg.absolute ? 1 : 0 );
-      hrange_i8( sh, sg.quant, 4 ); hrange_i8( sh, sg.lf, 4 );
       HashPlan::Chain c;
       c.is_map = true; c.map_off = plan.maps.size();
-      c.job = aa::hash_segment_map_job( nullptr, ps.width(), ps.height(), ps.mb_width(), ps.mb_height(), sh, static_cast<uint32_t>( plan.chains.size() ) );
+      c.job = aa::hash_segment_map_job( nullptr, ps.width(), ps.height(), ps.mb_width(), ps.mb_height(), sp.seg, static_cast<uint32_t>( plan.chains.size() ) );
       const size_t map_bytes = size_t( ps.mb_width() ) * ps.mb_height();
       plan.maps.insert( plan.maps.end(), sg.map.data(), sg.map.data() + map_bytes );
       d.map_result = static_cast<int>( plan.chains.size() );
       plan.chains.push_back( c );
     }
-    const aa::FilterAdjustState & fa = ps.filter_adjustments();
-    if ( fa.enabled ) { d.filter = true; hrange_i8( d.filter_hash, fa.ref, 4 ); }
+    d.filter = ps.filter_adjustments().enabled; d.filter_hash = sp.filter;
     for ( int k = 0; k < 3; k++ ) d.refs[k] = hash_plan_raster( ctx, plan, call, s, s->cur_ref_slot[k] );
   }
   const aa_status st = hash_launch( ctx, plan, call );

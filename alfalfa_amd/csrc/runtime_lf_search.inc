@@ -1,4 +1,4 @@
-// runtime.cpp, part 9 of 9 (ABI): the encoder's loop-filter level search on the GPU (aa_stream_lf_search; its candidates are scored by
+// runtime.cpp, one of its pieces (ABI): the encoder's loop-filter level search on the GPU (aa_stream_lf_search; its candidates are scored by
 // quality_of_planes, runtime_quality.inc), x264's SSIM of planes in host memory (aa_ssim_host) and reference access.
 extern "C" {
 namespace {

@@ -1,4 +1,4 @@
-// runtime.cpp, part 2 of 9: the device pool (slabs, size classes, release epochs, compute-ordered recycling), events, launch timers.
+// runtime.cpp, one of its pieces: the device pool (slabs, size classes, release epochs, compute-ordered recycling), events, launch timers.
 namespace {
 
 aa_status set_device( aa_ctx * ctx ) { HIP_TRY( hipSetDevice( ctx->device ) ); return AA_OK; }
@@ -235,6 +235,17 @@ hipEvent_t get_event( aa_ctx * ctx )
 {
   if ( !ctx->free_events.empty() ) { hipEvent_t e = ctx->free_events.back(); ctx->free_events.pop_back(); return e; }
   hipEvent_t e = nullptr; (void) hipEventCreate( &e ); return e;
+}
+// `waiter` takes up what is queued on it from now on only when everything `ahead` holds now has run.  A null stream: no caller's
+// stream to order against (aa_render_rgb_async, quality_of_planes).  *ev: the owner's event, made at the first use; one serves
+// every call of the owner's, since a queued wait keeps the record it was queued behind.
+aa_status stream_waits_for( hipEvent_t * ev, hipStream_t waiter, hipStream_t ahead )
+{
+  if ( !waiter || !ahead ) return AA_OK;
+  if ( !*ev ) HIP_TRY( hipEventCreateWithFlags( ev, hipEventDisableTiming ) );
+  HIP_TRY( hipEventRecord( *ev, ahead ) );
+  HIP_TRY( hipStreamWaitEvent( waiter, *ev, 0 ) );
+  return AA_OK;
 }
 void drain_profile( aa_ctx * ctx )
 {

@@ -9,20 +9,10 @@ struct QualityPair { const uint8_t * a; int64_t stride_a; const uint8_t * b; int
 // device pool, which also holds the group values; the piece goes back by the compute-stream route.  Nothing comes to the host.
 aa_status quality_of_planes( aa_ctx * ctx, const QualityPair * pairs, int np, double * ssim_dev, uint64_t * sse_dev, hipStream_t consumer )
 {
-  const int bi = ctx->next_quality_buf;
-  aa_ctx::RgbBuf & qb = ctx->quality_bufs[bi];
-  ctx->next_quality_buf = ( ctx->next_quality_buf + 1 ) % aa_ctx::kBindBufs;
-  if ( qb.busy ) { HIP_TRY( hipEventSynchronize( qb.done ) ); qb.busy = false; }
   const size_t table_bytes = align_up( size_t( np ) * sizeof( aa_quality_job ) );
-  if ( qb.cap < table_bytes ) {
-    if ( qb.host ) (void) hipHostFree( qb.host );
-    qb.host = nullptr; qb.cap = 0;
-    const size_t cap = align_up( std::max<size_t>( 1536, size_t( np ) * 2 ) * sizeof( aa_quality_job ) );
-    HIP_TRY( hipHostMalloc( reinterpret_cast<void **>( &qb.host ), cap, hipHostMallocDefault ) );
-    qb.cap = cap;
-  }
-  for ( hipEvent_t * e : { &qb.done, &qb.before, &qb.after } ) if ( !*e ) HIP_TRY( hipEventCreateWithFlags( e, hipEventDisableTiming ) );
-  aa_quality_job * jobs = reinterpret_cast<aa_quality_job *>( qb.host );
+  JobRing::Entry * qb = nullptr;
+  if ( aa_status st = ctx->quality_ring.take( table_bytes, align_up( 1536 * sizeof( aa_quality_job ) ), &qb ) ) return st;
+  aa_quality_job * jobs = reinterpret_cast<aa_quality_job *>( qb->host );
   uint64_t floats = 0;
   uint32_t max_blocks = 0;
   for ( int i = 0; i < np; i++ ) {
@@ -44,22 +34,14 @@ aa_status quality_of_planes( aa_ctx * ctx, const QualityPair * pairs, int np, do
   if ( aa_status st = dev_alloc_compute( ctx, piece_bytes, &piece ) ) return st;
   // (only the compute stream touches the piece: the next owner's kernels are behind this call's)
   struct Back { aa_ctx * c; uint8_t * p; size_t b; ~Back() { dev_free_compute( c, p, b ); } } back { ctx, piece, piece_bytes };
-  if ( consumer ) {
-    HIP_TRY( hipEventRecord( qb.before, consumer ) );
-    HIP_TRY( hipStreamWaitEvent( ctx->compute, qb.before, 0 ) );
-  }
-  HIP_TRY( hipMemcpyAsync( piece, qb.host, size_t( np ) * sizeof( aa_quality_job ), hipMemcpyHostToDevice, ctx->compute ) );
-  HIP_TRY( hipEventRecord( qb.done, ctx->compute ) );
-  qb.busy = true;
+  if ( aa_status st = stream_waits_for( &ctx->quality_consumer_ev, ctx->compute, consumer ) ) return st;
+  HIP_TRY( hipMemcpyAsync( piece, qb->host, size_t( np ) * sizeof( aa_quality_job ), hipMemcpyHostToDevice, ctx->compute ) );
+  if ( aa_status st = ctx->quality_ring.mark( *qb, ctx->compute ) ) return st;
   if ( sse_dev ) HIP_TRY( hipMemsetAsync( sse_dev, 0, size_t( np ) * sizeof( uint64_t ), ctx->compute ) );
   if ( int e = aa::launch_quality( reinterpret_cast<const aa_quality_job *>( piece ), np, max_blocks, reinterpret_cast<float *>( piece + table_bytes ),
                                    ssim_dev, reinterpret_cast<unsigned long long *>( sse_dev ), ctx->compute ) )
     return hip_fail( static_cast<hipError_t>( e ), "k_quality_blocks / k_quality_sum" );
-  if ( consumer ) {
-    HIP_TRY( hipEventRecord( qb.after, ctx->compute ) );
-    HIP_TRY( hipStreamWaitEvent( consumer, qb.after, 0 ) );
-  }
-  return AA_OK;
+  return stream_waits_for( &ctx->quality_consumer_ev, consumer, ctx->compute );
 }
 } // namespace
 
@@ -74,12 +56,7 @@ aa_status aa_quality_batch_async( aa_ctx * ctx, aa_stream * const * streams, int
   if ( aa_status st = set_device( ctx ) ) return st;
   for ( int i = 0; i < n; i++ ) {
     const aa_stream * s = streams[i];
-    if ( !s || s->ctx != ctx ) return fail( AA_ERR_ARGUMENT, "aa_quality_batch_async: stream belongs to another context" );
-    const int fi = frame_index[i];
-    if ( fi < 0 || fi >= static_cast<int>( s->frames.size() ) ) return fail( AA_ERR_ARGUMENT, "aa_quality_batch_async: bad frame index" );
-    const FrameRec & r = s->frames[fi];
-    if ( !r.handle_held ) return fail( AA_ERR_LOGIC, "aa_quality_batch_async: frame was released" );
-    if ( fi >= s->next_submit || !r.placed ) return fail( AA_ERR_LOGIC, "aa_quality_batch_async: frame not decoded yet" );
+    if ( aa_status st = held_decoded_frame( "aa_quality_batch_async", ctx, s, frame_index[i], nullptr ) ) return st;
     const aa_quality_ref & o = originals[i];
     if ( !o.y || ( planes == AA_QUALITY_YUV && ( !o.u || !o.v ) ) ) return fail( AA_ERR_ARGUMENT, "aa_quality_batch_async: null plane in original " + std::to_string( i ) );
     if ( o.y_stride < int64_t( s->pw ) || ( planes == AA_QUALITY_YUV && o.uv_stride < int64_t( s->pw / 2 ) ) )

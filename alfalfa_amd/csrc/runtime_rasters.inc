@@ -1,13 +1,13 @@
-// runtime.cpp, part 8 of 9 (ABI): rasters going out and coming in (downloads, batched delivery, references), decoder state (export /
+// runtime.cpp, one of its pieces (ABI): rasters going out and coming in (downloads, batched delivery, references), decoder state (export /
 // import, the reference's wire format), hashes and minihash.
 extern "C" {
 aa_status aa_stream_download( aa_stream * s, int fi, uint8_t * y, uint8_t * u, uint8_t * v )
 {
-  if ( !s || fi < 0 || fi >= static_cast<int>( s->frames.size() ) ) return fail( AA_ERR_ARGUMENT, "aa_stream_download: bad frame index" );
+  if ( !s ) return fail( AA_ERR_ARGUMENT, "aa_stream_download: bad frame index" );
+  const FrameRec * rp = nullptr;
+  if ( aa_status st = held_decoded_frame( "aa_stream_download", s->ctx, s, fi, &rp ) ) return st;
   if ( aa_status st = set_device( s->ctx ) ) return st;
-  const FrameRec & r = s->frames[fi];
-  if ( !r.handle_held ) return fail( AA_ERR_LOGIC, "aa_stream_download: frame was released" );
-  if ( fi >= s->next_submit ) return fail( AA_ERR_LOGIC, "aa_stream_download: frame not decoded yet" );
+  const FrameRec & r = *rp;
   HIP_TRY( hipStreamSynchronize( s->ctx->compute ) );
   if ( aa_status st = check_watchdog( s->ctx ) ) return st;
   uint8_t * dst[3] = { y, u, v };
@@ -29,11 +29,11 @@ void aa_pinned_free( void * p ) { if ( p ) (void) hipHostFree( p ); }
  * compute stream holds now; the planes (pinned memory) are valid after aa_ctx_sync or aa_stream_download_wait. */
 aa_status aa_stream_download_async( aa_stream * s, int fi, uint8_t * y, uint8_t * u, uint8_t * v )
 {
-  if ( !s || fi < 0 || fi >= static_cast<int>( s->frames.size() ) ) return fail( AA_ERR_ARGUMENT, "aa_stream_download_async: bad frame index" );
+  if ( !s ) return fail( AA_ERR_ARGUMENT, "aa_stream_download_async: bad frame index" );
+  const FrameRec * rp = nullptr;
+  if ( aa_status st = held_decoded_frame( "aa_stream_download_async", s->ctx, s, fi, &rp ) ) return st;
   if ( aa_status st = set_device( s->ctx ) ) return st;
-  const FrameRec & r = s->frames[fi];
-  if ( !r.handle_held ) return fail( AA_ERR_LOGIC, "aa_stream_download_async: frame was released" );
-  if ( fi >= s->next_submit || !r.placed ) return fail( AA_ERR_LOGIC, "aa_stream_download_async: frame not decoded yet" );
+  const FrameRec & r = *rp;
   aa_ctx * ctx = s->ctx;
   hipEvent_t e = get_event( ctx );
   HIP_TRY( hipEventRecord( e, ctx->compute ) );
@@ -80,53 +80,40 @@ aa_status aa_download_batch_async( aa_ctx * ctx, aa_stream * const * streams, in
   size_t max_bytes = 0;
   for ( int i = 0; i < n; i++ ) {
     const aa_stream * s = streams[i];
-    if ( !s || s->ctx != ctx ) return fail( AA_ERR_ARGUMENT, "aa_download_batch_async: stream belongs to another context" );
-    const int fi = frame_index[i];
-    if ( fi < 0 || fi >= static_cast<int>( s->frames.size() ) ) return fail( AA_ERR_ARGUMENT, "aa_download_batch_async: bad frame index" );
-    const FrameRec & r = s->frames[fi];
-    if ( !r.handle_held ) return fail( AA_ERR_LOGIC, "aa_download_batch_async: frame was released" );
-    if ( fi >= s->next_submit || !r.placed ) return fail( AA_ERR_LOGIC, "aa_download_batch_async: frame not decoded yet" );
+    if ( aa_status st = held_decoded_frame( "aa_download_batch_async", ctx, s, frame_index[i], nullptr ) ) return st;
     const size_t bytes = s->plane_bytes[0] + 2 * s->plane_bytes[1];
     if ( bytes > stride ) return fail( AA_ERR_ARGUMENT, "aa_download_batch_async: stride smaller than a raster" );
     max_bytes = std::max( max_bytes, bytes );
   }
   if ( stride & 15 ) return fail( AA_ERR_ARGUMENT, "aa_download_batch_async: stride must be a multiple of 16" );
-  const int gi = ctx->next_gather_buf;
-  aa_ctx::GatherBuf & gb = ctx->gather_bufs[gi];
-  ctx->next_gather_buf = ( ctx->next_gather_buf + 1 ) % aa_ctx::kBindBufs;
-  if ( gb.busy ) { HIP_TRY( hipEventSynchronize( gb.done ) ); gb.busy = false; }
-  // The buffer comes round again.  If its previous download is still on the list (more than kBindBufs queued and nobody waited for
-  // it), its copy may still be writing the caller's memory, and gb.copied -- the only handle on it -- is recorded anew below: the copy
-  // is waited for HERE, before the index leaves the list, so that aa_ctx_download_wait_until never counts a running copy as arrived.
-  if ( gb.copied && std::find( ctx->downloads_in_flight.begin(), ctx->downloads_in_flight.end(), gi ) != ctx->downloads_in_flight.end() )
-    HIP_TRY( hipEventSynchronize( gb.copied ) );
+  // The entry that comes round now.  If its previous download is still on the list (more than kBindBufs queued and nobody waited for
+  // it), its copy may still be writing the caller's memory, and its `copied` event -- the only handle on it -- is recorded anew below:
+  // the copy is waited for HERE, before the index leaves the list, so that aa_ctx_download_wait_until never counts a running copy as
+  // arrived.
+  const int gi = ctx->gather_ring.next;
+  hipEvent_t & copied = ctx->gather_copied[gi];
+  if ( copied && std::find( ctx->downloads_in_flight.begin(), ctx->downloads_in_flight.end(), gi ) != ctx->downloads_in_flight.end() )
+    HIP_TRY( hipEventSynchronize( copied ) );
   for ( auto it = ctx->downloads_in_flight.begin(); it != ctx->downloads_in_flight.end(); ) it = *it == gi ? ctx->downloads_in_flight.erase( it ) : it + 1;
-  if ( gb.cap < static_cast<size_t>( n ) ) {
-    if ( gb.host ) (void) hipHostFree( gb.host );
-    gb.host = nullptr; gb.dev = nullptr; gb.cap = 0;
-    const size_t cap = std::max<size_t>( 512, size_t( n ) * 2 );
-    HIP_TRY( hipHostMalloc( reinterpret_cast<void **>( &gb.host ), cap * sizeof( aa_gather_job ), hipHostMallocDefault ) );
-    HIP_TRY( hipHostGetDevicePointer( reinterpret_cast<void **>( &gb.dev ), gb.host, 0 ) );
-    gb.cap = cap;
-  }
-  if ( !gb.done ) HIP_TRY( hipEventCreateWithFlags( &gb.done, hipEventDisableTiming ) );
-  if ( !gb.copied ) HIP_TRY( hipEventCreateWithFlags( &gb.copied, hipEventDisableTiming ) );
+  JobRing::Entry * gb = nullptr;
+  if ( aa_status st = ctx->gather_ring.take( size_t( n ) * sizeof( aa_gather_job ), 512 * sizeof( aa_gather_job ), &gb ) ) return st;
+  if ( !copied ) HIP_TRY( hipEventCreateWithFlags( &copied, hipEventDisableTiming ) );
+  aa_gather_job * jobs = reinterpret_cast<aa_gather_job *>( gb->host );
   for ( int i = 0; i < n; i++ ) {
     aa_stream * s = streams[i];
-    gb.host[i].src = s->slots[s->frames[frame_index[i]].out_slot].dev;          // (Y, U, V back to back: slot_plane)
-    gb.host[i].bytes = s->plane_bytes[0] + 2 * s->plane_bytes[1];
+    jobs[i].src = s->slots[s->frames[frame_index[i]].out_slot].dev;          // (Y, U, V back to back: slot_plane)
+    jobs[i].bytes = s->plane_bytes[0] + 2 * s->plane_bytes[1];
   }
   const size_t total = stride * static_cast<size_t>( n );
   uint8_t * staging = nullptr;
   if ( aa_status st = dev_alloc( ctx, total, &staging ) ) return st;
   // (the piece goes back behind the copy that reads it: the epoch that frees it waits for the copy stream as well)
   struct Back { aa_ctx * c; uint8_t * p; size_t b; ~Back() { { std::lock_guard<std::mutex> g( c->pool_mu ); c->copy_reads_rasters = true; } dev_free( c, p, b, true ); } } back { ctx, staging, total };
-  if ( int e = aa::launch_gather_rasters( gb.dev, n, staging, stride, max_bytes, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_gather_rasters" );
-  HIP_TRY( hipEventRecord( gb.done, ctx->compute ) );
-  gb.busy = true;
-  HIP_TRY( hipStreamWaitEvent( ctx->copy, gb.done, 0 ) );
+  if ( int e = aa::launch_gather_rasters( reinterpret_cast<const aa_gather_job *>( gb->dev ), n, staging, stride, max_bytes, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_gather_rasters" );
+  if ( aa_status st = ctx->gather_ring.mark( *gb, ctx->compute ) ) return st;
+  HIP_TRY( hipStreamWaitEvent( ctx->copy, gb->done, 0 ) );
   HIP_TRY( hipMemcpyAsync( dst, staging, total, hipMemcpyDeviceToHost, ctx->copy ) );
-  HIP_TRY( hipEventRecord( gb.copied, ctx->copy ) );
+  HIP_TRY( hipEventRecord( copied, ctx->copy ) );
   ctx->downloads_in_flight.push_back( gi );
   return AA_OK;
 }
@@ -143,7 +130,7 @@ aa_status aa_ctx_download_wait_until( aa_ctx * ctx, int max_in_flight )
   if ( !ctx || max_in_flight < 0 ) return fail( AA_ERR_ARGUMENT, "aa_ctx_download_wait_until: bad argument" );
   if ( aa_status st = set_device( ctx ) ) return st;
   while ( static_cast<int>( ctx->downloads_in_flight.size() ) > max_in_flight ) {
-    HIP_TRY( hipEventSynchronize( ctx->gather_bufs[ctx->downloads_in_flight.front()].copied ) );
+    HIP_TRY( hipEventSynchronize( ctx->gather_copied[ctx->downloads_in_flight.front()] ) );
     ctx->downloads_in_flight.pop_front();
   }
   return check_watchdog( ctx );
@@ -161,7 +148,7 @@ aa_status aa_stream_raster_device( aa_stream * s, int fi, void ** y, void ** u, 
 
 /* Shown frames as RGB in the caller's device memory (VideoDisplay::draw's shader, display.cc): one k_render_rgb launch on the compute
  * stream for the lot, behind the decode of every frame it reads -- rasters are recycled in compute-stream order, so none can be
- * written under it.  Job list and float table go through a ring of pinned buffers (like the gather lists of aa_download_batch_async). */
+ * written under it.  Float table and job list go through a ring of pinned tables into the call's piece of the device pool. */
 aa_status aa_render_rgb_async( aa_ctx * ctx, aa_stream * const * streams, int n, const int * frame_index, int format,
                                const aa_rgb_target * targets, const double mean[3], const double std[3], void * consumer_stream )
 {
@@ -176,12 +163,7 @@ aa_status aa_render_rgb_async( aa_ctx * ctx, aa_stream * const * streams, int n,
   uint64_t max_threads = 0;
   for ( int i = 0; i < n; i++ ) {
     const aa_stream * s = streams[i];
-    if ( !s || s->ctx != ctx ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: stream belongs to another context" );
-    const int fi = frame_index[i];
-    if ( fi < 0 || fi >= static_cast<int>( s->frames.size() ) ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: bad frame index" );
-    const FrameRec & r = s->frames[fi];
-    if ( !r.handle_held ) return fail( AA_ERR_LOGIC, "aa_render_rgb_async: frame was released" );
-    if ( fi >= s->next_submit || !r.placed ) return fail( AA_ERR_LOGIC, "aa_render_rgb_async: frame not decoded yet" );
+    if ( aa_status st = held_decoded_frame( "aa_render_rgb_async", ctx, s, frame_index[i], nullptr ) ) return st;
     const aa_rgb_target & t = targets[i];
     const int64_t w = s->parser.width(), h = s->parser.height();
     if ( !t.dst ) return fail( AA_ERR_ARGUMENT, "aa_render_rgb_async: null dst" );
@@ -190,24 +172,11 @@ aa_status aa_render_rgb_async( aa_ctx * ctx, aa_stream * const * streams, int n,
     max_threads = std::max<uint64_t>( max_threads, uint64_t( ( w + 15 ) / 16 ) * uint64_t( ( h + 1 ) / 2 ) );
   }
   constexpr size_t kTableBytes = 768 * sizeof( uint32_t );
-  const int bi = ctx->next_rgb_buf;
-  aa_ctx::RgbBuf & rb = ctx->rgb_bufs[bi];
-  ctx->next_rgb_buf = ( ctx->next_rgb_buf + 1 ) % aa_ctx::kBindBufs;
-  if ( rb.busy ) { HIP_TRY( hipEventSynchronize( rb.done ) ); rb.busy = false; }
   const size_t bytes = kTableBytes + size_t( n ) * sizeof( aa_rgb_job );
-  if ( rb.cap < bytes ) {
-    if ( rb.dev ) HIP_TRY( hipStreamSynchronize( ctx->compute ) );      // (a render queued 16 calls ago may still read it)
-    if ( rb.host ) (void) hipHostFree( rb.host );
-    if ( rb.dev ) (void) hipFree( rb.dev );
-    rb.host = rb.dev = nullptr; rb.cap = 0;
-    const size_t cap = kTableBytes + std::max<size_t>( 512, size_t( n ) * 2 ) * sizeof( aa_rgb_job );
-    HIP_TRY( hipHostMalloc( reinterpret_cast<void **>( &rb.host ), cap, hipHostMallocDefault ) );
-    HIP_TRY( hipMalloc( reinterpret_cast<void **>( &rb.dev ), cap ) );
-    rb.cap = cap;
-  }
-  for ( hipEvent_t * e : { &rb.done, &rb.before, &rb.after } ) if ( !*e ) HIP_TRY( hipEventCreateWithFlags( e, hipEventDisableTiming ) );
+  JobRing::Entry * rb = nullptr;
+  if ( aa_status st = ctx->rgb_ring.take( bytes, kTableBytes + 512 * sizeof( aa_rgb_job ), &rb ) ) return st;
   // float formats: out = T_c[rgb], T_c[i] = (i / 255 - mean_c) / std_c in double, rounded to float, then to half / bfloat16 (nearest even)
-  uint32_t * table = reinterpret_cast<uint32_t *>( rb.host );
+  uint32_t * table = reinterpret_cast<uint32_t *>( rb->host );
   if ( is_float )
     for ( int c = 0; c < 3; c++ )
       for ( int i = 0; i < 256; i++ ) {
@@ -224,7 +193,7 @@ aa_status aa_render_rgb_async( aa_ctx * ctx, aa_stream * const * streams, int n,
         }
         table[c * 256 + i] = bits;
       }
-  aa_rgb_job * jobs = reinterpret_cast<aa_rgb_job *>( rb.host + kTableBytes );
+  aa_rgb_job * jobs = reinterpret_cast<aa_rgb_job *>( rb->host + kTableBytes );
   for ( int i = 0; i < n; i++ ) {
     aa_stream * s = streams[i];
     const int slot = s->frames[frame_index[i]].out_slot;
@@ -238,22 +207,19 @@ aa_status aa_render_rgb_async( aa_ctx * ctx, aa_stream * const * streams, int n,
     j.groups = ( j.width + 15 ) / 16;
     j.pad = 0;
   }
+  // the kernel reads table and jobs out of device memory: the call's piece of the pool, which only the compute stream touches (the
+  // next owner's kernels are behind this call's)
+  uint8_t * piece = nullptr;
+  if ( aa_status st = dev_alloc_compute( ctx, bytes, &piece ) ) return st;
+  struct Back { aa_ctx * c; uint8_t * p; size_t b; ~Back() { dev_free_compute( c, p, b ); } } back { ctx, piece, bytes };
   const hipStream_t consumer = static_cast<hipStream_t>( consumer_stream );
-  if ( consumer ) {
-    HIP_TRY( hipEventRecord( rb.before, consumer ) );
-    HIP_TRY( hipStreamWaitEvent( ctx->compute, rb.before, 0 ) );
-  }
-  HIP_TRY( hipMemcpyAsync( rb.dev, rb.host, bytes, hipMemcpyHostToDevice, ctx->compute ) );
-  HIP_TRY( hipEventRecord( rb.done, ctx->compute ) );
-  rb.busy = true;
-  if ( int e = aa::launch_render_rgb( reinterpret_cast<const aa_rgb_job *>( rb.dev + kTableBytes ), n, format, reinterpret_cast<const uint32_t *>( rb.dev ),
+  if ( aa_status st = stream_waits_for( &ctx->rgb_consumer_ev, ctx->compute, consumer ) ) return st;
+  HIP_TRY( hipMemcpyAsync( piece, rb->host, bytes, hipMemcpyHostToDevice, ctx->compute ) );
+  if ( aa_status st = ctx->rgb_ring.mark( *rb, ctx->compute ) ) return st;
+  if ( int e = aa::launch_render_rgb( reinterpret_cast<const aa_rgb_job *>( piece + kTableBytes ), n, format, reinterpret_cast<const uint32_t *>( piece ),
                                       static_cast<uint32_t>( max_threads ), ctx->compute ) )
     return hip_fail( static_cast<hipError_t>( e ), "k_render_rgb" );
-  if ( consumer ) {
-    HIP_TRY( hipEventRecord( rb.after, ctx->compute ) );
-    HIP_TRY( hipStreamWaitEvent( consumer, rb.after, 0 ) );
-  }
-  return AA_OK;
+  return stream_waits_for( &ctx->rgb_consumer_ev, consumer, ctx->compute );
 }
 
 aa_status aa_stream_references( const aa_stream * s, int * last, int * golden, int * alternate )
@@ -386,34 +352,39 @@ aa_status aa_stream_import_reference_host( aa_stream * s, const uint8_t * y, con
   return import_common( s, src, hipMemcpyHostToDevice );
 }
 
-/* ---------------- hashes: boost::hash_combine / hash_range as the reference uses them (pre-1.81 formula) ---------------- */
+/* ---------------- hashes (hcombine / hrange_*: runtime_types.inc) ---------------- */
 namespace {
-inline void hcombine( uint64_t & seed, uint64_t v ) { seed ^= v + 0x9e3779b9ull + ( seed << 6 ) + ( seed >> 2 ); }
-inline void hrange_u8( uint64_t & seed, const uint8_t * p, size_t n ) { for ( size_t i = 0; i < n; i++ ) hcombine( seed, p[i] ); }
-inline void hrange_i8( uint64_t & seed, const int8_t * p, size_t n ) { for ( size_t i = 0; i < n; i++ ) hcombine( seed, static_cast<uint64_t>( static_cast<int64_t>( p[i] ) ) ); }
-
 // DecoderState::hash (decoder.cc:266-281) with ProbabilityTables::hash (probability_tables.cc:36-57), Segmentation::hash
 // (decoder.cc:379-394; the map is sized by the frame's PIXEL dimensions, decoder.cc:238) and FilterAdjustments::hash
 // (decoder.cc:331-340 -- whose second range runs from mode_adjustments.begin() to REF_adjustments.end(), i.e. is empty: the
 // mode adjustments are not hashed; kept as is).
-uint64_t state_hash( const aa::Parser & ps )
+// ... everything but the walk over the segment map.  head: dimensions and probability tables; seg: the segmentation header, the
+// seed the map's chain starts from (segmentation on); filter: the adjustments (adjustments on)
+struct StateHashParts { uint64_t head = 0, seg = 0, filter = 0; };
+void state_hash_parts( const aa::Parser & ps, StateHashParts & out )
 {
   const aa::ProbTables & t = ps.probs();
   uint64_t ph = 0;
   hrange_u8( ph, &t.coeff[0][0][0][0], 1056 ); hrange_u8( ph, t.y_mode, 4 ); hrange_u8( ph, t.uv_mode, 3 ); hrange_u8( ph, &t.mv[0][0], 38 );
-  uint64_t h = 0;
-  hcombine( h, ps.width() ); hcombine( h, ps.height() ); hcombine( h, ph );
+  hcombine( out.head, ps.width() ); hcombine( out.head, ps.height() ); hcombine( out.head, ph );
+  const aa::SegmentationState & sg = ps.segmentation();
+  if ( sg.enabled ) { hcombine( out.seg, sg.absolute ? 1 : 0 ); hrange_i8( out.seg, sg.quant, 4 ); hrange_i8( out.seg, sg.lf, 4 ); }
+  const aa::FilterAdjustState & fa = ps.filter_adjustments();
+  if ( fa.enabled ) hrange_i8( out.filter, fa.ref, 4 );
+}
+uint64_t state_hash( const aa::Parser & ps )
+{
+  StateHashParts parts;
+  state_hash_parts( ps, parts );
+  uint64_t h = parts.head;
   const aa::SegmentationState & sg = ps.segmentation();
   if ( sg.enabled ) {
-    uint64_t sh = 0;
-    hcombine( sh, sg.absolute ? 1 : 0 );
-    hrange_i8( sh, sg.quant, 4 ); hrange_i8( sh, sg.lf, 4 );
+    uint64_t sh = parts.seg;
     const unsigned w = ps.width(), hgt = ps.height(), mbw = ps.mb_width(), mbh = ps.mb_height();
     for ( unsigned r = 0; r < hgt; r++ ) for ( unsigned c = 0; c < w; c++ ) hcombine( sh, ( r < mbh && c < mbw ) ? sg.map[size_t( r ) * mbw + c] : 3 );
     hcombine( h, sh );
   }
-  const aa::FilterAdjustState & fa = ps.filter_adjustments();
-  if ( fa.enabled ) { uint64_t fh = 0; hrange_i8( fh, fa.ref, 4 ); hcombine( h, fh ); }
+  if ( ps.filter_adjustments().enabled ) hcombine( h, parts.filter );
   return h;
 }
 
@@ -451,12 +422,11 @@ aa_status aa_stream_state_hash( aa_stream * s, uint64_t * out )
 }
 aa_status aa_stream_raster_hash( aa_stream * s, int fi, uint64_t * out )
 {
-  if ( !s || !out || fi < 0 || fi >= static_cast<int>( s->frames.size() ) ) return fail( AA_ERR_ARGUMENT, "aa_stream_raster_hash: bad argument" );
+  if ( !s || !out ) return fail( AA_ERR_ARGUMENT, "aa_stream_raster_hash: bad argument" );
+  const FrameRec * r = nullptr;
+  if ( aa_status st = held_decoded_frame( "aa_stream_raster_hash", s->ctx, s, fi, &r ) ) return st;
   if ( aa_status st = set_device( s->ctx ) ) return st;
-  const FrameRec & r = s->frames[fi];
-  if ( fi >= s->next_submit || !r.placed ) return fail( AA_ERR_LOGIC, "aa_stream_raster_hash: frame not decoded yet" );
-  if ( !r.handle_held ) return fail( AA_ERR_LOGIC, "aa_stream_raster_hash: frame was released" );
-  return slot_hash( s, r.out_slot, out );
+  return slot_hash( s, r->out_slot, out );
 }
 /* DecoderHash (decoder.cc:143-153,482-490): state, last, golden, alternative; everything parsed must have been submitted */
 aa_status aa_stream_decoder_hash( aa_stream * s, uint64_t parts[4], uint64_t * whole )

@@ -1,4 +1,4 @@
-// runtime.cpp, part 4 of 9: a frame's records and rasters -- release, pinned staging, job records, References bookkeeping (bind_frame).
+// runtime.cpp, one of its pieces: a frame's records and rasters -- release, pinned staging, job records, References bookkeeping (bind_frame).
 
 static uint8_t * slot_plane( aa_stream * s, int slot, int plane )
 {
@@ -136,34 +136,34 @@ aa_status bind_batch( aa_ctx * ctx, aa_stream * const * streams, int n, const in
   int need = 0;
   for ( int i = 0; i < n; i++ ) if ( !streams[i]->frames[frame_index[i]].placed ) need++;
   if ( !need ) return AA_OK;
-  aa_ctx::BindBuf & bb = ctx->bind_bufs[ctx->next_bind_buf];
-  ctx->next_bind_buf = ( ctx->next_bind_buf + 1 ) % aa_ctx::kBindBufs;
-  if ( bb.busy ) {
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY( hipEventSynchronize( bb.done ) );
-    bb.busy = false;
-    ctx->stats.bind_wait_ms += std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - t0 ).count();
-  }
-  if ( bb.cap < static_cast<size_t>( need ) ) {
-    if ( bb.host ) (void) hipHostFree( bb.host );
-    bb.host = nullptr; bb.dev = nullptr; bb.cap = 0;
-    const size_t cap = std::max<size_t>( 512, size_t( need ) * 2 );
-    // pinned and mapped: the patch kernel reads the bindings over the bus.  (No copy engine on the reconstruction path: a small
-    // copy queues behind whatever the engine holds, and that can be a copy ordered behind a seconds-long parse kernel.)
-    HIP_TRY( hipHostMalloc( reinterpret_cast<void **>( &bb.host ), cap * sizeof( aa_raster_binding ), hipHostMallocDefault ) );
-    HIP_TRY( hipHostGetDevicePointer( reinterpret_cast<void **>( &bb.dev ), bb.host, 0 ) );
-    bb.cap = cap;
-  }
-  if ( !bb.done ) HIP_TRY( hipEventCreateWithFlags( &bb.done, hipEventDisableTiming ) );
+  // pinned and mapped: the patch kernel reads the bindings over the bus.  (No copy engine on the reconstruction path: a small
+  // copy queues behind whatever the engine holds, and that can be a copy ordered behind a seconds-long parse kernel.)
+  JobRing::Entry * bb = nullptr;
+  double waited_ms = 0;
+  if ( aa_status st = ctx->bind_ring.take( size_t( need ) * sizeof( aa_raster_binding ), 512 * sizeof( aa_raster_binding ), &bb, nullptr, &waited_ms ) ) return st;
+  ctx->stats.bind_wait_ms += waited_ms;
+  aa_raster_binding * bindings = reinterpret_cast<aa_raster_binding *>( bb->host );
   int k = 0;
   for ( int i = 0; i < n; i++ ) {
     if ( streams[i]->frames[frame_index[i]].placed ) continue;
-    if ( aa_status st = bind_frame( streams[i], frame_index[i], &bb.host[k] ) ) return st;
+    if ( aa_status st = bind_frame( streams[i], frame_index[i], &bindings[k] ) ) return st;
     k++;
   }
-  if ( int e = aa::launch_bind_rasters( bb.dev, k, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_bind_rasters" );
-  HIP_TRY( hipEventRecord( bb.done, ctx->compute ) );
-  bb.busy = true;
+  if ( int e = aa::launch_bind_rasters( reinterpret_cast<const aa_raster_binding *>( bb->dev ), k, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_bind_rasters" );
+  return ctx->bind_ring.mark( *bb, ctx->compute );
+}
+
+// A decoded frame of this context that the caller still holds: what every call that reads a frame's raster asks first.  `who`: the
+// ABI call, in front of the message; *out (may be null): the frame.
+aa_status held_decoded_frame( const char * who, aa_ctx * ctx, const aa_stream * s, int fi, const FrameRec ** out )
+{
+  const auto no = [who]( aa_status code, const char * what ) { return fail( code, std::string( who ) + ": " + what ); };
+  if ( !s || s->ctx != ctx ) return no( AA_ERR_ARGUMENT, "stream belongs to another context" );
+  if ( fi < 0 || fi >= static_cast<int>( s->frames.size() ) ) return no( AA_ERR_ARGUMENT, "bad frame index" );
+  const FrameRec & r = s->frames[fi];
+  if ( !r.handle_held ) return no( AA_ERR_LOGIC, "frame was released" );
+  if ( fi >= s->next_submit || !r.placed ) return no( AA_ERR_LOGIC, "frame not decoded yet" );
+  if ( out ) *out = &r;
   return AA_OK;
 }
 

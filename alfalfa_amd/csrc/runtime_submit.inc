@@ -1,4 +1,4 @@
-// runtime.cpp, part 6 of 9 (ABI): frames coming in -- host-parsed frames and frames given as records, aa_submit_frames (routing: GPU lanes,
+// runtime.cpp, one of its pieces (ABI): frames coming in -- host-parsed frames and frames given as records, aa_submit_frames (routing: GPU lanes,
 // host lanes, a worker per stream), the hand-over to the token workers, the host lanes' worker threads.
 namespace {
 // A frame whose records are produced on the HOST -- by the bitstream parser (aa_stream_parse) or handed in as records

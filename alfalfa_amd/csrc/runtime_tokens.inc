@@ -1,4 +1,4 @@
-// runtime.cpp, part 3 of 9: the token workers' host side -- job queue, coefficient heap (virtual range, growth, chunk pool), worker grids
+// runtime.cpp, one of its pieces: the token workers' host side -- job queue, coefficient heap (virtual range, growth, chunk pool), worker grids
 // (launch, top-up, retirement), the mirrored counters, waiting for a frame's `done` word.
 namespace {
 // ---------------- token workers: job queue, coefficient heap, worker grids ----------------

@@ -1,6 +1,6 @@
-// runtime.cpp, part 1 of 9 (one translation unit, #included in order by runtime.cpp): error reporting, the cores a process really gets,
-// and the records behind the ABI -- frame-store chunks, the batch of a submit call, raster slots, frame records, the context (aa_ctx:
-// streams, device pool, token-worker state, host lanes) and the stream (aa_stream).
+// runtime.cpp, the first of its pieces (one translation unit, #included in order by runtime.cpp): error reporting, the cores a process
+// really gets, and the records behind the ABI -- the ring of pinned job tables, frame-store chunks, the batch of a submit call, raster
+// slots, frame records, the context (aa_ctx: streams, device pool, token-worker state, host lanes) and the stream (aa_stream).
 namespace {
 
 thread_local std::string g_last_error;
@@ -64,6 +64,58 @@ aa_status hip_fail( hipError_t e, const char * what )
 constexpr size_t kChunkBytes = size_t( 64 ) << 20;
 constexpr size_t kAlign = 256;
 inline size_t align_up( size_t v, size_t a = kAlign ) { return ( v + a - 1 ) / a * a; }
+
+// boost::hash_combine / hash_range as the reference uses them (pre-1.81 formula)
+inline void hcombine( uint64_t & seed, uint64_t v ) { seed ^= v + 0x9e3779b9ull + ( seed << 6 ) + ( seed >> 2 ); }
+inline void hrange_u8( uint64_t & seed, const uint8_t * p, size_t n ) { for ( size_t i = 0; i < n; i++ ) hcombine( seed, p[i] ); }
+inline void hrange_i8( uint64_t & seed, const int8_t * p, size_t n ) { for ( size_t i = 0; i < n; i++ ) hcombine( seed, static_cast<uint64_t>( static_cast<int64_t>( p[i] ) ) ); }
+
+// The job table of a batched call (raster bindings, gather list, render jobs, scoring jobs, hash chains) is written by the host and
+// read by the device, and the host runs ahead of the device: each kind of call has a ring of kBindBufs pinned tables.  `done` is
+// recorded (mark) behind the last device command that reads the table; take() waits for it when the entry comes round again.
+constexpr int kBindBufs = 16;               // calls of one kind the host may run ahead of the device
+struct JobRing {
+  struct Entry {
+    uint8_t * host = nullptr;               // pinned
+    uint8_t * dev = nullptr;                // `host` as the device sees it: what a kernel that reads the table over the bus is given
+    size_t cap = 0;                         // bytes
+    hipEvent_t done = nullptr;
+    bool busy = false;
+  };
+  Entry entries[kBindBufs];
+  int next = 0;                             // the entry the next take() hands out
+  // The next entry, free and with room for `bytes` (grown to twice the need, at least floor_bytes); *waited_ms: the wait for its last user
+  aa_status take( size_t bytes, size_t floor_bytes, Entry ** out, int * index = nullptr, double * waited_ms = nullptr )
+  {
+    const int i = next;
+    Entry & e = entries[i];
+    next = ( next + 1 ) % kBindBufs;
+    if ( e.busy ) {
+      const auto t0 = std::chrono::steady_clock::now();
+      HIP_TRY( hipEventSynchronize( e.done ) );
+      e.busy = false;
+      if ( waited_ms ) *waited_ms = std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - t0 ).count();
+    }
+    if ( e.cap < bytes ) {
+      if ( e.host ) (void) hipHostFree( e.host );
+      e.host = e.dev = nullptr; e.cap = 0;
+      const size_t cap = align_up( std::max( floor_bytes, bytes * 2 ) );
+      HIP_TRY( hipHostMalloc( reinterpret_cast<void **>( &e.host ), cap, hipHostMallocDefault ) );
+      HIP_TRY( hipHostGetDevicePointer( reinterpret_cast<void **>( &e.dev ), e.host, 0 ) );
+      e.cap = cap;
+    }
+    if ( !e.done ) HIP_TRY( hipEventCreateWithFlags( &e.done, hipEventDisableTiming ) );
+    *out = &e;
+    if ( index ) *index = i;
+    return AA_OK;
+  }
+  // `st` has been given the last command that reads the entry's table
+  aa_status mark( Entry & e, hipStream_t st ) { HIP_TRY( hipEventRecord( e.done, st ) ); e.busy = true; return AA_OK; }
+  void destroy()
+  {
+    for ( Entry & e : entries ) { if ( e.host ) (void) hipHostFree( e.host ); if ( e.done ) (void) hipEventDestroy( e.done ); e = Entry(); }
+  }
+};
 
 struct Chunk {
   uint8_t * host = nullptr;   // pinned
@@ -152,10 +204,7 @@ struct aa_ctx {
   std::atomic<int> refs { 1 };   // the context handle + one per stream: freed by whoever drops the last (bindings may finalise in any order)
   // device-side entropy decode: submit calls rotate over a few HIP streams so that the parse of one batch runs beside the
   // parse of the next and beside reconstruction (a parse is a few thousand latency-bound chains, not a chip-filling kernel)
-  struct BindBuf { aa_raster_binding * host = nullptr, * dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false; };
-  static constexpr int kBindBufs = 16;      // aa_decode_batch calls the host may run ahead of the compute stream
-  BindBuf bind_bufs[kBindBufs];
-  int next_bind_buf = 0;
+  JobRing bind_ring;                        // the raster bindings of an aa_decode_batch call (bind_batch), read by k_bind_rasters over the bus
   // HOST LANES: host cores in the role of token lanes.  A frame handed to them (AA_SUBMIT_HOST on a call with many streams: the key
   // frames a pipeline needs at once -- 35 ms on a core, 2 s as a chain on a GPU lane) has had its header pre-pass like every frame
   // of the device route; a worker thread parses macroblock headers and tokens from the batch arena's pinned copy (aa::parse_frame_body),
@@ -171,22 +220,18 @@ struct aa_ctx {
     std::atomic<uint64_t> parsed_bytes { 0 }, parse_us { 0 }, backlog_bytes { 0 };
     uint64_t parse_us_mark = 0;          // parse_us at the last aa_ctx_kernel_stats reset
   } host_lanes;
-  // the raster list of a batched download (aa_download_batch_async), read by k_gather_rasters over the bus
-  struct GatherBuf { aa_gather_job * host = nullptr, * dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr, copied = nullptr; bool busy = false; };
-  GatherBuf gather_bufs[kBindBufs];
-  int next_gather_buf = 0;
-  // the job list and float table of a render (aa_render_rgb_async): written to `host` (pinned), copied to `dev` on the compute stream
-  // ahead of k_render_rgb; `done` fires when the copy has read `host`.  before / after: the waits on the caller's stream
-  struct RgbBuf { uint8_t * host = nullptr, * dev = nullptr; size_t cap = 0; hipEvent_t done = nullptr, before = nullptr, after = nullptr; bool busy = false; };
-  RgbBuf rgb_bufs[kBindBufs];
-  int next_rgb_buf = 0;
-  // the job table of a scoring call (aa_quality_batch_async): written to `host`, copied into the call's pool piece (`dev` stays null)
-  RgbBuf quality_bufs[kBindBufs];
-  int next_quality_buf = 0;
-  // batched hashes (runtime_hashes.inc): a stream of their own, a ring of pinned buffers (result table, job table, segment maps: read
-  // and written by k_hash_chains over the bus) and the calls whose results nobody has committed yet, oldest first
+  // the raster list of a batched download (aa_download_batch_async), read by k_gather_rasters over the bus; gather_copied[i]: recorded
+  // on the COPY stream behind the copy of the call that has entry i (downloads_in_flight lists such entries)
+  JobRing gather_ring;
+  hipEvent_t gather_copied[kBindBufs] = {};
+  // the float table and job list of a render (aa_render_rgb_async) and the job table of a scoring call (quality_of_planes): copied on
+  // the compute stream into the call's piece of the device pool; `done` fires when the copy has read the entry
+  JobRing rgb_ring, quality_ring;
+  hipEvent_t rgb_consumer_ev = nullptr, quality_consumer_ev = nullptr;   // stream_waits_for: the caller's stream and the compute stream waiting for each other
+  // batched hashes (runtime_hashes.inc): a stream of their own, a ring of pinned tables (result table, job table, segment maps: read
+  // and written by k_hash_chains over the bus; an entry is its call's until hash_commit_oldest has read the results out of it) and the
+  // calls whose results nobody has committed yet, oldest first.  ready[i]: compute stream -> hash stream, for the call that has entry i
   struct Hash {
-    struct Buf { uint8_t * host = nullptr, * dev = nullptr; size_t cap = 0; hipEvent_t ready = nullptr, done = nullptr; };
     struct Value { uint64_t value = 0; int result = -1; };      // result >= 0: word `result` of the call's result table, else `value`
     struct Fill { aa_stream * s; int slot; int result; };        // a raster the call holds; result >= 0: its Slot cache is filled at the wait
     struct Decoder { uint64_t state = 0; int map_result = -1; bool filter = false; uint64_t filter_hash = 0; Value refs[3]; };
@@ -198,13 +243,14 @@ struct aa_ctx {
     };
     std::mutex mu;
     hipStream_t st = nullptr;
-    Buf bufs[kBindBufs];
-    int next_buf = 0, simds = 0;
+    JobRing ring;
+    hipEvent_t ready[kBindBufs] = {};
+    int simds = 0;
     std::deque<Call> calls;
     uint64_t stats[4] = { 0, 0, 0, 0 };      // chains launched, bytes walked, rasters answered from the cache, cache entries filled
   } hash;
   int row_handoff_by_kernel[2] = { 0, 0 };   // (diagnostics: waits the second look ended, k_recon_intra4 / k_loopfilter_rows4)
-  std::deque<int> downloads_in_flight;   // gather_bufs whose copy (aa_download_batch_async) nobody has waited for yet, oldest first
+  std::deque<int> downloads_in_flight;   // gather_ring entries whose copy (aa_download_batch_async) nobody has waited for yet, oldest first
   // A parse batch holds its stream for as long as its longest chain (seconds for a key frame): a batch queued behind another
   // one on the same stream starts that much later.  Hence one stream per batch that can be in flight, and a batch goes to a
   // stream that has nothing queued (pick_parse_stream).
