@@ -12,3 +12,4 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 from .decoder import AlfalfaError, Context, Decoder, FilePlayer, Parser, Quality, psnr, read_ivf  # noqa: F401
+from .capi import quant_factors  # noqa: F401

@@ -81,6 +81,12 @@ class QualityRef(C.Structure):
     _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("y_stride", C.c_int64), ("uv_stride", C.c_int64)]
 
 
+class RebaseJob(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("hdr", C.POINTER(FrameHeader)), ("mbs", C.c_void_p), ("target", QualityRef),
+                ("mbs_out", C.c_void_p), ("coeffs_out", C.c_void_p), ("coeff_capacity_blocks", C.c_size_t),
+                ("num_coeff_blocks", C.c_uint32), ("frame_index", C.c_int)]
+
+
 class AlfalfaError(RuntimeError):
     """Mirrors the reference's exception types (exception.hh:76-98) by name in `.kind`."""
 
@@ -136,6 +142,9 @@ SYMBOLS = [
     ("aa_render_rgb_async", C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(RgbTarget),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     ("aa_quality_batch_async", C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.POINTER(QualityRef), C.c_int, _P, _P, _P]),
+    ("aa_rebase_batch", C.c_int, [_P, C.POINTER(RebaseJob), C.c_int]),
+    ("aa_rebase_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("aa_quant_factors", None, [C.c_int, C.POINTER(C.c_int8), C.POINTER(C.c_uint16)]),
     ("aa_stream_references", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("aa_stream_reference_slots", C.c_int, [_P, C.POINTER(C.c_int)]),
     ("aa_stream_import_reference", C.c_int, [_P, _P, _P, _P]),
@@ -194,6 +203,19 @@ def check(rc):
 
 def device_count():
     return lib().aa_device_count()
+
+
+def quant_factors(qi, deltas=None):
+    """Quantizer::Quantizer( QuantIndices ) (quantization.cc:83-93) -> [y_dc, y_ac, y2_dc, y2_ac, uv_dc, uv_ac] for the base index qi
+    and the header's deltas (y_dc, y2_dc, y2_ac, uv_dc, uv_ac), None = all zero: a new frame header's quant[0] (aa_quant_factors)."""
+    out = (C.c_uint16 * 6)()
+    d = None
+    if deltas is not None:
+        if len(deltas) != 5:
+            raise ValueError("quant_factors: deltas are (y_dc, y2_dc, y2_ac, uv_dc, uv_ac)")
+        d = (C.c_int8 * 5)(*deltas)
+    lib().aa_quant_factors(int(qi), d, out)
+    return list(out)
 
 
 def raster_geometry(width, height):

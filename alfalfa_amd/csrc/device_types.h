@@ -62,6 +62,23 @@ struct aa_quality_job {
   uint64_t out_off;            // the plane's first group value in the workspace (floats; a multiple of 4)
 };
 
+// One (stream, new frame) of a rebase (aa_rebase_batch): the prediction frame's records, the references they predict from, the target
+// planes, and where the forward path's results go.  The kernels read nothing else.
+#define AA_REBASE_MB_BYTES ( 25 * 16 * 2 )   // dense coefficient scratch per macroblock: 25 slots (0..15 Y, 16..19 U, 20..23 V, 24 Y2) of 16 int16
+struct aa_rebase_dev_job {
+  const uint8_t * ref[4][3];   // [1] last, [2] golden, [3] altref planes of the job's stream ([0] unused)
+  const uint8_t * target[3];   // padded, edge-extended planes the new frame stands for
+  int64_t target_stride[2];    // bytes: luma, chroma
+  uint8_t * recon[3];          // unfiltered reconstruction of the new frame (padded planes, stride = padded width): intra prediction reads it
+  const aa_mb_info * mbs;      // mbw * mbh records of the prediction frame (modes, ref_frame, vectors, b_modes)
+  int16_t * coeffs;            // [mbw * mbh][25][16]
+  uint32_t * masks;            // [mbw * mbh]: bit b = slot b holds a non-zero coefficient
+  uint16_t quant[6];           // {y_dc, y_ac, y2_dc, y2_ac, uv_dc, uv_ac} of the new frame
+  uint16_t mbw, mbh;
+  uint32_t has_intra;          // some macroblock is intra: the reconstruction is needed
+  uint32_t pad;
+};
+
 #define AA_MAX_XCD 16
 
 #define AA_SYNC_WS_DUMP 140
@@ -151,4 +168,7 @@ int launch_hash_chains( const HashJob * jobs, int n, int lanes_per_wave, uint64_
 // quality_kernels.hip: jobs[i] (n_planes of them) -> ssim[i], sse[i] (optional; zeroed by the caller): k_quality_blocks over
 // max_blocks x n_planes workgroups (max_blocks: the largest job's strips * chunks), then k_quality_sum; group_values: the workspace
 int launch_quality( const aa_quality_job * jobs, int n_planes, uint32_t max_blocks, float * group_values, double * ssim, unsigned long long * sse, void * stream );
+// rebase_kernels.hip: jobs[i] (n of them; max_mbs: the largest job's macroblocks) -> dense coefficients, masks and the unfiltered
+// reconstruction: k_rebase_inter over every inter macroblock, then (any_intra) k_rebase_intra, one wave per job
+int launch_rebase( const aa_rebase_dev_job * jobs, int n, uint32_t max_mbs, bool any_intra, void * stream );
 }

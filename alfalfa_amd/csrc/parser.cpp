@@ -81,6 +81,12 @@ Quantizer make_quantizer( int y_ac_qi, const int delta[5] /* y_dc, y2_dc, y2_ac,
 
 } // namespace
 
+void quant_factors( int y_ac_qi, const int delta[5], uint16_t out[6] )
+{
+  const Quantizer q = make_quantizer( y_ac_qi, delta );
+  for ( int i = 0; i < 6; i++ ) out[i] = q.f[i];
+}
+
 void ProbTables::set_defaults()
 {
   std::memcpy( coeff, k_default_coeff_probs, sizeof coeff );

@@ -122,4 +122,7 @@ private:
 // scratch; mbs: fp.mbw * fp.mbh records; coeff_out: worst case 25 * 16 int16 per macroblock.
 void parse_frame_body( const uint8_t * data, const FrameParams & fp, aa_mb_info * mbs, int16_t * coeff_out, uint8_t * above_nz, uint32_t * coeff_blocks, uint32_t * intra_mbs );
 
+// Quantizer::Quantizer( QuantIndices ) (quantization.cc:83-93): out = {y_dc, y_ac, y2_dc, y2_ac, uv_dc, uv_ac}; delta = {y_dc, y2_dc, y2_ac, uv_dc, uv_ac}
+void quant_factors( int y_ac_qi, const int delta[5], uint16_t out[6] );
+
 } // namespace aa

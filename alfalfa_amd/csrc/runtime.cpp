@@ -42,7 +42,7 @@
 #include "coeff_pack.hh"
 #include "hash_chain.hh"
 
-// ONE translation unit, this file and the eleven it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
+// ONE translation unit, this file and the twelve it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
 // the pieces share file-local state (the anonymous-namespace helpers, g_last_error) and are #included in dependency order.
 #include "runtime_types.inc"
 #include "runtime_pool.inc"
@@ -55,3 +55,4 @@
 #include "runtime_hashes.inc"
 #include "runtime_quality.inc"
 #include "runtime_lf_search.inc"
+#include "runtime_rebase.inc"

@@ -227,6 +227,8 @@ struct aa_ctx {
   // the float table and job list of a render (aa_render_rgb_async) and the job table of a scoring call (quality_of_planes): copied on
   // the compute stream into the call's piece of the device pool; `done` fires when the copy has read the entry
   JobRing rgb_ring, quality_ring;
+  double rebase_timing[5] = {};             // aa_rebase_last_timing
+  JobRing rebase_ring;                      // the job table and input records of a rebase slice (aa_rebase_batch), copied on the compute stream into the slice's piece
   hipEvent_t rgb_consumer_ev = nullptr, quality_consumer_ev = nullptr;   // stream_waits_for: the caller's stream and the compute stream waiting for each other
   // batched hashes (runtime_hashes.inc): a stream of their own, a ring of pinned tables (result table, job table, segment maps: read
   // and written by k_hash_chains over the bus; an entry is its call's until hash_commit_oldest has read the results out of it) and the

@@ -69,6 +69,47 @@ AA_MHD Quad iwht_pass2( int i0, int i1, int i2, int i3 )     // row i -> DC of Y
   return q;
 }
 
+// ---- forward 4x4 DCT (DCTCoefficients::subtract_dct, dct.cc:45-104): what the rebase runs backwards ----
+// First (horizontal) pass over one ROW of residuals (target - prediction, -255..255): coefficients 0..3 of that row.
+AA_MHD Quad fdct_pass1( int r0, int r1, int r2, int r3 )
+{
+  const int a1 = ( r0 + r3 ) * 8, b1 = ( r1 + r2 ) * 8, c1 = ( r1 - r2 ) * 8, d1 = ( r0 - r3 ) * 8;
+  Quad q;
+  q.v0 = static_cast<int16_t>( a1 + b1 ); q.v1 = static_cast<int16_t>( ( c1 * 2217 + d1 * 5352 + 14500 ) >> 12 );
+  q.v2 = static_cast<int16_t>( a1 - b1 ); q.v3 = static_cast<int16_t>( ( d1 * 2217 - c1 * 5352 + 7500 ) >> 12 );
+  return q;
+}
+// Second (vertical) pass over one COLUMN of first-pass results (rows 0..3): the coefficients at i, i+4, i+8, i+12.
+AA_MHD Quad fdct_pass2( int i0, int i4, int i8, int i12 )
+{
+  const int a1 = i0 + i12, b1 = i4 + i8, c1 = i4 - i8, d1 = i0 - i12;
+  Quad q;
+  q.v0 = static_cast<int16_t>( ( a1 + b1 + 7 ) >> 4 ); q.v1 = static_cast<int16_t>( ( ( c1 * 2217 + d1 * 5352 + 12000 ) >> 16 ) + ( d1 != 0 ) );
+  q.v2 = static_cast<int16_t>( ( a1 - b1 + 7 ) >> 4 ); q.v3 = static_cast<int16_t>( ( d1 * 2217 - c1 * 5352 + 51000 ) >> 16 );
+  return q;
+}
+
+// ---- forward Walsh-Hadamard (DCTCoefficients::wht, dct.cc:106-164) over the 16 luma DCs, raster order ----
+AA_MHD Quad fwht_pass1( int i0, int i1, int i2, int i3 )   // row i of the DCs -> entries 4i .. 4i+3
+{
+  const int a1 = ( i0 + i2 ) * 4, d1 = ( i1 + i3 ) * 4, c1 = ( i1 - i3 ) * 4, b1 = ( i0 - i2 ) * 4;
+  Quad q;
+  q.v0 = static_cast<int16_t>( a1 + d1 + ( a1 != 0 ) ); q.v1 = static_cast<int16_t>( b1 + c1 );
+  q.v2 = static_cast<int16_t>( b1 - c1 ); q.v3 = static_cast<int16_t>( a1 - d1 );
+  return q;
+}
+AA_MHD int fwht_round( int x ) { return static_cast<int16_t>( ( x + ( x < 0 ) + 3 ) >> 3 ); }
+AA_MHD Quad fwht_pass2( int c0, int c4, int c8, int c12 )  // column i of the first pass -> entries i, i+4, i+8, i+12
+{
+  const int a1 = c0 + c8, d1 = c4 + c12, c1 = c4 - c12, b1 = c0 - c8;
+  Quad q;
+  q.v0 = fwht_round( a1 + d1 ); q.v1 = fwht_round( b1 + c1 ); q.v2 = fwht_round( b1 - c1 ); q.v3 = fwht_round( a1 - d1 );
+  return q;
+}
+
+// ---- quantisation (DCTCoefficients::quantize, quantization.cc:148-157): integer division truncating toward zero ----
+AA_MHD int quantize( int coeff, int factor ) { return static_cast<int16_t>( coeff / factor ); }
+
 // ---- six-tap sub-pixel filter: one output of one pass, clamped to u8 (Q6) ----
 AA_MHD int sixtap_coeff( int frac, int tap )
 {

@@ -355,6 +355,67 @@ class Context:
             cur.wait_stream(compute)
         return Quality(ssim, sse)
 
+    def rebase(self, decoders, headers, mbs, targets):
+        """The rebase (aa_rebase_batch; Encoder::update_residues, reencode.cc:236-303), one new frame per decoder: headers[i] (a dict
+        as Parser.parse / frame_header return it: quant[0] are the factors divided by, key_frame 0) and mbs[i] (the prediction frame's
+        records: modes, references and vectors are kept) with residues recomputed so that the frame decodes to targets[i] from
+        decoders[i]'s current references.  targets[i]: (y, u, v) uint8 device tensors of the padded plane shapes, edge-extended by the
+        caller (rows may be padded), or one contiguous uint8 device tensor holding the three padded planes back to back.
+        -> per job (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]) in the shapes Decoder.read_records returns; the frame is
+        appended to its decoder and is decoded like any other (Context.decode_batch).  Synchronous."""
+        import torch
+        n = len(decoders)
+        if n == 0 or len(headers) != n or len(mbs) != n or len(targets) != n:
+            raise ValueError("rebase: need as many headers, records and targets as decoders, and at least one")
+        device = torch.device("cuda", self.device)
+        jobs = (capi.RebaseJob * n)()
+        keep, outs = [], []
+        for i, (d, header, mb, t) in enumerate(zip(decoders, headers, mbs, targets)):
+            pw, ph = d.padded_width, d.padded_height
+            shapes = [(ph, pw), (ph // 2, pw // 2), (ph // 2, pw // 2)]
+            if isinstance(t, torch.Tensor):
+                if t.dtype != torch.uint8 or t.device != device or not t.is_contiguous() or t.numel() != pw * ph * 3 // 2:
+                    raise ValueError("rebase: targets[%d] must be a contiguous torch.uint8 tensor of %d bytes on %s" % (i, pw * ph * 3 // 2, device))
+                flat = t.reshape(-1)
+                t = (flat[:pw * ph].view(shapes[0]), flat[pw * ph:pw * ph * 5 // 4].view(shapes[1]), flat[pw * ph * 5 // 4:].view(shapes[2]))
+            if len(t) != 3:
+                raise ValueError("rebase: targets[%d] must be a tensor or (y, u, v)" % i)
+            for p, (pl, shape) in enumerate(zip(t, shapes)):
+                if tuple(pl.shape) != shape or pl.dtype != torch.uint8 or pl.device != device or pl.stride(1) != 1 or pl.stride(0) < shape[1]:
+                    raise ValueError("rebase: targets[%d]: plane %d must be torch.uint8 of shape %s on %s with contiguous rows" % (i, p, shape, device))
+            if t[1].stride(0) != t[2].stride(0):
+                raise ValueError("rebase: targets[%d]: u and v must have the same row stride" % i)
+            hdr = FrameHeader()
+            for name, _ in FrameHeader._fields_:
+                if name == "quant":
+                    for sgm in range(4):
+                        for k in range(6):
+                            hdr.quant[sgm][k] = header["quant"][sgm][k]
+                else:
+                    setattr(hdr, name, header[name])
+            nmb = hdr.mb_width * hdr.mb_height
+            rec = np.ascontiguousarray(mb, dtype=MB_INFO_DTYPE).reshape(-1)
+            if len(rec) != nmb:
+                raise ValueError("rebase: mbs[%d] holds %d records, the header says %d" % (i, len(rec), nmb))
+            mb_out = np.zeros(nmb, dtype=MB_INFO_DTYPE)
+            cf = np.zeros((nmb * 25, 16), dtype=np.int16)
+            j = jobs[i]
+            j.stream, j.hdr, j.mbs = d.h, C.pointer(hdr), rec.ctypes.data_as(C.c_void_p)
+            j.target.y, j.target.u, j.target.v = t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr()
+            j.target.y_stride, j.target.uv_stride = t[0].stride(0), t[1].stride(0)
+            j.mbs_out, j.coeffs_out, j.coeff_capacity_blocks = mb_out.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p), len(cf)
+            keep.append((hdr, rec, t))
+            outs.append((mb_out, cf, hdr.mb_width, hdr.mb_height))
+        torch.cuda.current_stream(device).synchronize()      # (the targets are ready; the call itself waits for its kernels)
+        capi.check(self.L.aa_rebase_batch(self.h, jobs, n))
+        return [(jobs[i].frame_index, mb_out.reshape(mbh, mbw), cf[:jobs[i].num_coeff_blocks].copy()) for i, (mb_out, cf, mbw, mbh) in enumerate(outs)]
+
+    def rebase_timing(self):
+        """The last rebase of this context (aa_rebase_last_timing), ms: call, upload + kernels, download, host records, append."""
+        out = (C.c_double * 5)()
+        capi.check(self.L.aa_rebase_last_timing(self.h, out))
+        return dict(zip(("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms"), out))
+
     def _hash_streams(self, what, decoders):
         n = len(decoders)
         if n == 0:
@@ -477,6 +538,10 @@ class Decoder:
         fi = C.c_int()
         capi.check(self.L.aa_stream_append_records(self.h, C.byref(hdr), mbs.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p), C.byref(fi)))
         return fi.value
+
+    def rebase(self, header, mb, target):
+        """One new frame of this decoder by rebase (Context.rebase) -> (frame_index, mb [mbh, mbw], coeff_blocks [n, 16])."""
+        return self.ctx.rebase([self], [header], [mb], [target])[0]
 
     def upload(self):
         capi.check(self.L.aa_stream_upload(self.h))

@@ -471,6 +471,37 @@ void aa_raster_geometry( uint16_t width, uint16_t height, uint32_t * padded_widt
 aa_status aa_stream_lf_search( aa_stream * s, const uint8_t * data, size_t size, const uint8_t * original_luma,
                                int level_lo, int level_hi, int * best_level, double * best_ssim, double * ssim_out, uint8_t * rasters_out );
 
+/* The REBASE (Encoder::update_residues, reencode.cc:131-303, what xc-enc -r does with every inter frame of a chunk): the
+ * prediction frame's modes and motion vectors are kept and its residues recomputed against the references the stream holds NOW, so
+ * that the new frame decodes to the target picture from there -- predict, subtract from the target, forward DCT (WHT of the luma DCs
+ * where a Y2 block is coded), plain division by the new header's factors, reconstruct (intra macroblocks predict from the new
+ * frame's own unfiltered reconstruction).  One job = one (stream, new frame); jobs are independent and run as one pair of kernels on
+ * the compute stream.  The call is synchronous: it returns with the records in the caller's arrays -- what aa_parser_parse would make
+ * of the serialised frame (token probabilities and Frame::serialize stay with the caller) -- and the frame appended to its stream as
+ * aa_stream_append_records appends it: decode it with aa_decode_batch like any other frame (the stream's DecoderState is not advanced).
+ * Errors (AA_ERR_ARGUMENT unless noted; nothing is appended to any stream of the call): key_frame set; segmentation_enabled
+ * (AA_ERR_UNSUPPORTED: the reference quantises with the frame quantiser whatever the segment); null pointers; a header of another size;
+ * a stream listed twice; a stream with a frame appended but not decoded (AA_ERR_LOGIC); coeff_capacity_blocks too small (the message
+ * names the count needed; 25 per macroblock always suffice). */
+typedef struct aa_rebase_job {
+  aa_stream * stream;          /* predicted from ITS references; the new frame is appended to it */
+  const aa_frame_header * hdr; /* header of the NEW frame: quant[0][*] are the factors used for division and reconstruction; loop filter
+                                  fields, refresh / copy flags, sign bias as the caller wants them; key_frame must be 0 */
+  const aa_mb_info * mbs;      /* prediction frame's records (aa_parser_parse / aa_stream_read_records): modes, ref_frame, vectors, b_modes,
+                                  split_partition, segment_id, lf_level are taken; flags' residual bits, nz_mask, coeff_index are ignored */
+  aa_quality_ref target;       /* DEVICE planes of the padded size, edge-extended by the caller */
+  aa_mb_info * mbs_out; int16_t * coeffs_out; size_t coeff_capacity_blocks;   /* host */
+  uint32_t num_coeff_blocks; int frame_index;                                  /* out */
+} aa_rebase_job;
+aa_status aa_rebase_batch( aa_ctx * ctx, aa_rebase_job * jobs, int n );
+/* Where the last successful aa_rebase_batch of the context spent its time, in ms: out[0] the whole call (wall clock); [1] job table up
+ * and the two kernels, [2] coefficients and masks down (HIP events on the compute stream, summed over the call's slices); [3] the
+ * records built on the host, [4] the frames appended (wall clock).  For tools/rebase_probe.py. */
+aa_status aa_rebase_last_timing( aa_ctx * ctx, double out[5] );
+/* Quantizer::Quantizer( QuantIndices ) (quantization.cc:83-93): out = {y_dc, y_ac, y2_dc, y2_ac, uv_dc, uv_ac} for the base index
+ * y_ac_qi and the header's deltas {y_dc, y2_dc, y2_ac, uv_dc, uv_ac} (NULL: all zero) -- aa_frame_header::quant[0] of a new frame. */
+void aa_quant_factors( int y_ac_qi, const int8_t deltas[5], uint16_t out[6] );
+
 /* BaseRaster::quality (util/raster.cc:63-66: x264's SSIM of two planes, stride = width) for planes in HOST memory. */
 aa_status aa_ssim_host( const uint8_t * a, const uint8_t * b, int width, int height, double * out );
 

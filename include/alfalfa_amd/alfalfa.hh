@@ -808,6 +808,25 @@ public:
     return { static_cast<uint8_t>( best ), q };
   }
 
+  // The rebase of Encoder::update_residues (reencode.cc:236-303; Encoder::reencode's option 4) for ONE new frame of this decoder
+  // (aa_rebase_batch with one job; many decoders at once: the C call): `records` are the prediction frame's macroblock records,
+  // `header` the new frame's (quant[0]: aa_quant_factors), `target` the padded, edge-extended planes in DEVICE memory.  Modes and
+  // vectors are kept, residues recomputed against this decoder's current references.  -> index of the frame appended to the
+  // stream (decode it with aa_decode_batch); records_out / coefficients_out: what the serialiser needs (parse order).
+  int rebase( const aa_frame_header & header, const aa_mb_info * records, const aa_quality_ref & target,
+              std::vector<aa_mb_info> & records_out, std::vector<int16_t> & coefficients_out )
+  {
+    const size_t nmb = size_t( header.mb_width ) * header.mb_height;
+    records_out.resize( nmb ); coefficients_out.resize( nmb * 25 * 16 );
+    aa_rebase_job job;
+    std::memset( &job, 0, sizeof job );
+    job.stream = owner_->stream; job.hdr = &header; job.mbs = records; job.target = target;
+    job.mbs_out = records_out.data(); job.coeffs_out = coefficients_out.data(); job.coeff_capacity_blocks = nmb * 25;
+    check( aa_rebase_batch( owner_->ctx->get(), &job, 1 ) );
+    coefficients_out.resize( size_t( job.num_coeff_blocks ) * 16 );
+    return job.frame_index;
+  }
+
   static std::vector<std::pair<bool, RasterHandle>> get_frame_outputs( const std::vector<Decoder *> & decoders, const std::vector<Chunk> & frames )
   {
     if ( decoders.size() != frames.size() || decoders.empty() ) throw std::invalid_argument( "get_frame_outputs: one frame per decoder" );
