@@ -87,6 +87,12 @@ class RebaseJob(C.Structure):
                 ("num_coeff_blocks", C.c_uint32), ("frame_index", C.c_int)]
 
 
+class ReencodeJob(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("hdr", C.POINTER(FrameHeader)), ("target", QualityRef), ("quality", C.c_int), ("append", C.c_int),
+                ("mbs_out", C.c_void_p), ("coeffs_out", C.c_void_p), ("coeff_capacity_blocks", C.c_size_t),
+                ("num_coeff_blocks", C.c_uint32), ("frame_index", C.c_int)]
+
+
 class AlfalfaError(RuntimeError):
     """Mirrors the reference's exception types (exception.hh:76-98) by name in `.kind`."""
 
@@ -144,6 +150,9 @@ SYMBOLS = [
     ("aa_quality_batch_async", C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.POINTER(QualityRef), C.c_int, _P, _P, _P]),
     ("aa_rebase_batch", C.c_int, [_P, C.POINTER(RebaseJob), C.c_int]),
     ("aa_rebase_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("aa_reencode_batch", C.c_int, [_P, C.POINTER(ReencodeJob), C.c_int]),
+    ("aa_reencode_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("aa_ctx_set_reencode_slots", C.c_int, [_P, C.c_int]),
     ("aa_quant_factors", None, [C.c_int, C.POINTER(C.c_int8), C.POINTER(C.c_uint16)]),
     ("aa_stream_references", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("aa_stream_reference_slots", C.c_int, [_P, C.POINTER(C.c_int)]),

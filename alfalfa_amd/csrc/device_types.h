@@ -79,6 +79,16 @@ struct aa_rebase_dev_job {
   uint32_t pad;
 };
 
+// One (stream, new frame) of a re-encode (aa_reencode_batch): the rebase's job -- references, target, reconstruction, dense coefficient
+// slots, masks, quantiser; mbs unused, has_intra 1 -- and what the decision adds: the job's rate model, the records it writes, and a
+// side record per macroblock for the census and the B_PRED trial of its neighbours.
+struct aa_reencode_dev_job {
+  aa_rebase_dev_job base;
+  const void * costs;          // aa::ReencCosts (reencode_search.hh)
+  aa_mb_info * mbs_out;        // mbw * mbh records: y_mode, uv_mode, ref_frame, nz_mask and u are the kernel's, the rest is zero
+  uint32_t * nb;               // [mbw * mbh][4]: aa::ReencNeighbour
+};
+
 #define AA_MAX_XCD 16
 
 #define AA_SYNC_WS_DUMP 140
@@ -171,4 +181,7 @@ int launch_quality( const aa_quality_job * jobs, int n_planes, uint32_t max_bloc
 // rebase_kernels.hip: jobs[i] (n of them; max_mbs: the largest job's macroblocks) -> dense coefficients, masks and the unfiltered
 // reconstruction: k_rebase_inter over every inter macroblock, then (any_intra) k_rebase_intra, one wave per job
 int launch_rebase( const aa_rebase_dev_job * jobs, int n, uint32_t max_mbs, bool any_intra, void * stream );
+// reencode_kernels.hip: jobs[i] (n of them) -> records, dense coefficients, masks and the unfiltered reconstruction: k_reencode_inter, one
+// workgroup per job; slots: macroblocks of an anti-diagonal a round takes (1..16)
+int launch_reencode( const aa_reencode_dev_job * jobs, int n, int slots, void * stream );
 }

@@ -41,8 +41,9 @@
 #include "tok_fsm.hh"
 #include "coeff_pack.hh"
 #include "hash_chain.hh"
+#include "reencode_search.hh"
 
-// ONE translation unit, this file and the twelve it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
+// ONE translation unit, this file and the thirteen it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
 // the pieces share file-local state (the anonymous-namespace helpers, g_last_error) and are #included in dependency order.
 #include "runtime_types.inc"
 #include "runtime_pool.inc"
@@ -56,3 +57,4 @@
 #include "runtime_quality.inc"
 #include "runtime_lf_search.inc"
 #include "runtime_rebase.inc"
+#include "runtime_reencode.inc"

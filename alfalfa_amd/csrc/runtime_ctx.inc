@@ -163,6 +163,7 @@ aa_status aa_ctx_create( int device, aa_ctx ** out )
   if ( const char * e = std::getenv( "ALFALFA_AMD_SCHEDULE" ) ) ctx->schedule = std::string( e ) == "diagonal" ? 1 : 0;
   if ( const char * e = std::getenv( "ALFALFA_AMD_PACKED" ) ) ctx->tok.packed = atoi( e ) != 0;
   if ( const char * e = std::getenv( "ALFALFA_AMD_LANE_PER_PARTITION" ) ) ctx->tok.lane_per_partition = atoi( e ) != 0;
+  if ( const char * e = std::getenv( "ALFALFA_AMD_REENC_SLOTS" ) ) ctx->reenc_slots = std::max( 1, std::min( 16, atoi( e ) ) );
   if ( const char * e = std::getenv( "ALFALFA_AMD_HOST_SHARE_MS" ) ) ctx->host_share_ms = std::max( 0.0, atof( e ) );
   // The row-pipelined kernels keep every unit on one XCD (per-XCD ticket queues indexed by the hardware XCC_ID): find
   // out which XCC ids workgroups of this device really land on.  They must be 0..n-1, each reached by a modest grid.

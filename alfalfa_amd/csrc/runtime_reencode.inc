@@ -1,0 +1,211 @@
+// runtime.cpp (ABI): the re-encode (aa_reencode_batch) -- a chunk's key frame encoded again as an inter frame predicted from the job
+// streams' current references: the reference's mode decision and the forward path on the device (reencode_kernels.hip), the records
+// built on the host and appended as aa_stream_append_records appends them.  Modelled on aa_rebase_batch (runtime_rebase.inc), whose
+// job-table ring, slice bound and record builder it shares.
+namespace {
+
+// What the kernel left of a job -> the caller's records: flags, nz_mask and coeff_index by rebase_records, as the parser sets them for
+// the serialised frame; lf_level from the new header (mb_lf_level) with the stream's current filter adjustments; segment_id 0.
+RebaseCounts reencode_records( const aa_mb_info * in, const uint32_t * masks, const int16_t * dense, size_t nmb, const aa::HeaderParams & fp, aa_mb_info * out, int16_t * coeffs_out )
+{
+  const RebaseCounts c = rebase_records( in, masks, dense, nmb, out, coeffs_out );
+  if ( out ) for ( size_t i = 0; i < nmb; i++ ) out[i].lf_level = aa::mb_lf_level( fp, 0, out[i].ref_frame, out[i].y_mode );
+  return c;
+}
+
+} // namespace
+
+extern "C" {
+
+aa_status aa_ctx_set_reencode_slots( aa_ctx * ctx, int slots )
+{
+  if ( !ctx || slots < 1 || slots > 16 ) return fail( AA_ERR_ARGUMENT, "aa_ctx_set_reencode_slots: 1..16 macroblocks of an anti-diagonal per round" );
+  ctx->reenc_slots = slots;
+  return AA_OK;
+}
+
+aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
+{
+  const auto no = []( aa_status code, int i, const std::string & what ) { return fail( code, "aa_reencode_batch: job " + std::to_string( i ) + ": " + what ); };
+  if ( !ctx || !jobs || n <= 0 ) return fail( AA_ERR_ARGUMENT, "aa_reencode_batch: bad argument" );
+  if ( aa_status st = set_device( ctx ) ) return st;
+  // ---- 1. the arguments: nothing is launched, nothing appended unless every job of the call is good ----
+  for ( int i = 0; i < n; i++ ) {
+    aa_reencode_job & j = jobs[i];
+    if ( !j.stream || !j.hdr || !j.mbs_out || !j.target.y || !j.target.u || !j.target.v ) return no( AA_ERR_ARGUMENT, i, "null pointer" );
+    if ( !j.coeffs_out && j.coeff_capacity_blocks ) return no( AA_ERR_ARGUMENT, i, "null pointer" );
+    aa_stream * s = j.stream;
+    if ( s->ctx != ctx ) return no( AA_ERR_ARGUMENT, i, "stream belongs to another context" );
+    for ( int k = 0; k < i; k++ ) if ( jobs[k].stream == s ) return no( AA_ERR_ARGUMENT, i, "its stream is also job " + std::to_string( k ) + "'s: one new frame per stream and call" );
+    if ( j.hdr->key_frame ) return no( AA_ERR_ARGUMENT, i, "the new frame's header says key frame: a re-encode makes an inter frame" );
+    if ( j.hdr->segmentation_enabled ) return no( AA_ERR_UNSUPPORTED, i, "segmentation is enabled: the reference refuses it too (reencode.cc:47-49)" );
+    if ( j.quality != AA_REENCODE_BEST && j.quality != AA_REENCODE_REALTIME ) return no( AA_ERR_ARGUMENT, i, "quality is neither AA_REENCODE_BEST nor AA_REENCODE_REALTIME" );
+    const size_t nmb = size_t( s->parser.mb_width() ) * s->parser.mb_height();
+    if ( j.hdr->mb_width != s->parser.mb_width() || j.hdr->mb_height != s->parser.mb_height() || j.hdr->num_macroblocks != nmb )
+      return no( AA_ERR_ARGUMENT, i, "the header's macroblock dimensions are not this decoder's" );
+    if ( s->next_submit != static_cast<int>( s->frames.size() ) ) return no( AA_ERR_LOGIC, i, "its stream holds a frame that is appended but not decoded: the references are not current" );
+    if ( j.target.y_stride < int64_t( s->pw ) || j.target.uv_stride < int64_t( s->pw / 2 ) ) return no( AA_ERR_ARGUMENT, i, "row stride smaller than the padded plane's width" );
+    for ( int f = 0; f < 6; f++ ) if ( !j.hdr->quant[0][f] ) return no( AA_ERR_ARGUMENT, i, "a quantiser factor of the header is zero" );
+    if ( s->cur_ref_slot[0] < 0 || !s->slots[s->cur_ref_slot[0]].dev ) return no( AA_ERR_LOGIC, i, "its stream has no reference rasters" );
+    j.num_coeff_blocks = 0; j.frame_index = -1;
+  }
+
+  const double t_call = now_ms();
+  double ms_kernels = 0, ms_download = 0, ms_records = 0;
+  // ---- 2..5. slice by slice: job table and rate models up, the kernel, records, coefficients and masks down, records into the caller's arrays ----
+  const size_t share = rebase_slice_bytes( ctx );
+  std::vector<uint32_t> intra_mbs( n, 0 );
+  for ( int first = 0; first < n; ) {
+    int count = 0;
+    size_t dense_total = 0, masks_total = 0, records_total = 0, side_total = 0, raster_total = 0;
+    while ( first + count < n ) {
+      const aa_stream * s = jobs[first + count].stream;
+      const size_t nmb = size_t( s->parser.mb_width() ) * s->parser.mb_height();
+      if ( count && dense_total + nmb * AA_REBASE_MB_BYTES > share ) break;
+      dense_total += align_up( nmb * AA_REBASE_MB_BYTES ); masks_total += align_up( nmb * sizeof( uint32_t ) );
+      records_total += align_up( nmb * sizeof( aa_mb_info ) ); side_total += align_up( nmb * sizeof( aa::ReencNeighbour ) );
+      raster_total += s->slot_bytes;
+      count++;
+    }
+    // the pinned side: job table | every job's rate model (a JobRing entry, read by one copy); the device piece: the same, then per job
+    // masks | records | dense coefficients (the results, downloaded by one copy), then side records and reconstruction rasters
+    const size_t table_bytes = align_up( size_t( count ) * sizeof( aa_reencode_dev_job ) ), costs_bytes = align_up( sizeof( aa::ReencCosts ) );
+    const size_t up_bytes = table_bytes + size_t( count ) * costs_bytes, result_bytes = masks_total + records_total + dense_total;
+    const size_t piece_bytes = up_bytes + result_bytes + side_total + raster_total;
+    JobRing::Entry * rb = nullptr;
+    if ( aa_status st = ctx->rebase_ring.take( up_bytes, align_up( 64 * sizeof( aa_rebase_dev_job ) ), &rb ) ) return st;
+    uint8_t * piece = nullptr;
+    if ( aa_status st = dev_alloc_compute( ctx, piece_bytes, &piece ) ) return st;
+    struct Back { aa_ctx * c; uint8_t * p; size_t b; ~Back() { dev_free_compute( c, p, b ); } } back { ctx, piece, piece_bytes };
+    size_t staging_bytes = 0;
+    uint8_t * staging = pinned_get( ctx, result_bytes, &staging_bytes );
+    if ( !staging ) return fail( AA_ERR_HIP, "aa_reencode_batch: pinned staging allocation failed" );
+    struct Unpin { aa_ctx * c; uint8_t * p; size_t b; ~Unpin() { std::lock_guard<std::mutex> g( c->pool_mu ); c->pinned_pool.emplace_back( p, b ); } } unpin { ctx, staging, staging_bytes };
+
+    aa_reencode_dev_job * table = reinterpret_cast<aa_reencode_dev_job *>( rb->host );
+    std::vector<size_t> result_off( count );
+    std::vector<aa::HeaderParams> lf_params( count );
+    size_t up_off = table_bytes, res_off = 0, side_off = up_bytes + result_bytes;
+    for ( int k = 0; k < count; k++ ) {
+      const aa_reencode_job & j = jobs[first + k];
+      aa_stream * s = j.stream;
+      const size_t nmb = size_t( s->parser.mb_width() ) * s->parser.mb_height();
+      aa_reencode_dev_job & d = table[k];
+      std::memset( &d, 0, sizeof d );
+      for ( int p = 0; p < 3; p++ ) d.base.ref[1][p] = slot_plane( s, s->cur_ref_slot[0], p );          // every candidate predicts from LAST
+      d.base.target[0] = static_cast<const uint8_t *>( j.target.y ); d.base.target[1] = static_cast<const uint8_t *>( j.target.u ); d.base.target[2] = static_cast<const uint8_t *>( j.target.v );
+      d.base.target_stride[0] = j.target.y_stride; d.base.target_stride[1] = j.target.uv_stride;
+      // the rate model: the mode costs are constants, the vector costs come from the stream's CURRENT probabilities (reencode.cc:82-84)
+      aa::reenc_fill_costs( *reinterpret_cast<aa::ReencCosts *>( rb->host + up_off ), s->parser.probs().mv, j.quality );
+      d.costs = piece + up_off;
+      up_off += costs_bytes;
+      result_off[k] = res_off;
+      d.base.masks = reinterpret_cast<uint32_t *>( piece + up_bytes + res_off ); res_off += align_up( nmb * sizeof( uint32_t ) );
+      d.mbs_out = reinterpret_cast<aa_mb_info *>( piece + up_bytes + res_off ); res_off += align_up( nmb * sizeof( aa_mb_info ) );
+      d.base.coeffs = reinterpret_cast<int16_t *>( piece + up_bytes + res_off ); res_off += align_up( nmb * AA_REBASE_MB_BYTES );
+      d.nb = reinterpret_cast<uint32_t *>( piece + side_off ); side_off += align_up( nmb * sizeof( aa::ReencNeighbour ) );
+      uint8_t * raster = piece + side_off;
+      d.base.recon[0] = raster; d.base.recon[1] = raster + s->plane_bytes[0]; d.base.recon[2] = raster + s->plane_bytes[0] + s->plane_bytes[1];
+      side_off += s->slot_bytes;
+      std::memcpy( d.base.quant, j.hdr->quant[0], sizeof d.base.quant );
+      d.base.mbw = j.hdr->mb_width; d.base.mbh = j.hdr->mb_height; d.base.has_intra = 1;
+      // what mb_lf_level reads: the new header's level, the stream's current adjustments where the header keeps them switched on
+      aa::HeaderParams & fp = lf_params[k];
+      std::memset( &fp, 0, sizeof fp );
+      fp.loop_filter_level = j.hdr->loop_filter_level;
+      for ( int g = 0; g < 4; g++ ) fp.seg_level[g] = j.hdr->loop_filter_level;
+      const aa::FilterAdjustState & fa = s->parser.filter_adjustments();
+      if ( j.hdr->filter_adjustments_enabled && fa.enabled ) { fp.fadj_enabled = 1; std::memcpy( fp.fadj_ref, fa.ref, 4 ); std::memcpy( fp.fadj_mode, fa.mode, 4 ); }
+    }
+    hipEvent_t ev[3] = { get_event( ctx ), get_event( ctx ), get_event( ctx ) };      // (aa_reencode_last_timing: tables up + kernel, results down)
+    struct Events { aa_ctx * c; hipEvent_t * e; ~Events() { for ( int i = 0; i < 3; i++ ) if ( e[i] ) c->free_events.push_back( e[i] ); } } events { ctx, ev };
+    if ( !ev[0] || !ev[1] || !ev[2] ) return fail( AA_ERR_HIP, "aa_reencode_batch: hipEventCreate failed" );
+    HIP_TRY( hipEventRecord( ev[0], ctx->compute ) );
+    HIP_TRY( hipMemcpyAsync( piece, rb->host, up_bytes, hipMemcpyHostToDevice, ctx->compute ) );
+    if ( aa_status st = ctx->rebase_ring.mark( *rb, ctx->compute ) ) return st;
+    if ( int e = aa::launch_reencode( reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, ctx->reenc_slots, ctx->compute ) )
+      return hip_fail( static_cast<hipError_t>( e ), "k_reencode_inter" );
+    HIP_TRY( hipEventRecord( ev[1], ctx->compute ) );
+    HIP_TRY( hipMemcpyAsync( staging, piece + up_bytes, result_bytes, hipMemcpyDeviceToHost, ctx->compute ) );
+    HIP_TRY( hipEventRecord( ev[2], ctx->compute ) );
+    HIP_TRY( hipStreamSynchronize( ctx->compute ) );
+    if ( aa_status st = check_watchdog( ctx ) ) return st;
+    { float a = 0, b = 0; if ( hipEventElapsedTime( &a, ev[0], ev[1] ) == hipSuccess && hipEventElapsedTime( &b, ev[1], ev[2] ) == hipSuccess ) { ms_kernels += a; ms_download += b; } }
+    const double t_records = now_ms();
+
+    // records, one host worker per job at a time; a job whose coefficient array is too small stops the call
+    std::atomic<int> next { 0 }, short_job { -1 };
+    auto work = [&]() {
+      for ( ;; ) {
+        const int k = next.fetch_add( 1 );
+        if ( k >= count ) return;
+        aa_reencode_job & j = jobs[first + k];
+        const size_t nmb = size_t( j.hdr->mb_width ) * j.hdr->mb_height;
+        const uint8_t * at = staging + result_off[k];
+        const uint32_t * masks = reinterpret_cast<const uint32_t *>( at ); at += align_up( nmb * sizeof( uint32_t ) );
+        const aa_mb_info * recs = reinterpret_cast<const aa_mb_info *>( at ); at += align_up( nmb * sizeof( aa_mb_info ) );
+        const int16_t * dense = reinterpret_cast<const int16_t *>( at );
+        const RebaseCounts need = reencode_records( recs, masks, dense, nmb, lf_params[k], nullptr, nullptr );
+        j.num_coeff_blocks = need.blocks; intra_mbs[first + k] = need.intra;
+        if ( need.blocks > j.coeff_capacity_blocks ) { int none = -1; short_job.compare_exchange_strong( none, first + k ); continue; }
+        reencode_records( recs, masks, dense, nmb, lf_params[k], j.mbs_out, j.coeffs_out );
+      }
+    };
+    const int workers = std::max( 1, std::min( worker_threads( 0 ), count ) );
+    if ( workers == 1 ) work();
+    else {
+      std::vector<std::thread> pool;
+      for ( int t = 0; t < workers; t++ ) pool.emplace_back( work );
+      for ( auto & t : pool ) t.join();
+    }
+    ms_records += now_ms() - t_records;
+    if ( short_job >= 0 ) {
+      const int i = short_job;
+      return no( AA_ERR_ARGUMENT, i, "coefficient buffer too small: " + std::to_string( jobs[i].num_coeff_blocks ) + " blocks needed, room for " + std::to_string( jobs[i].coeff_capacity_blocks ) );
+    }
+    first += count;
+  }
+
+  // ---- 6. the frames whose job says so join their streams, as aa_stream_append_records appends them ----
+  const double t_append = now_ms();
+  {
+    std::vector<aa_status> status( n, AA_OK );
+    std::vector<std::string> message( n );
+    std::atomic<int> next { 0 };
+    auto work = [&]() {
+      (void) hipSetDevice( ctx->device );
+      for ( ;; ) {
+        const int i = next.fetch_add( 1 );
+        if ( i >= n ) return;
+        aa_reencode_job & j = jobs[i];
+        if ( !j.append ) continue;
+        aa_frame_header h = *j.hdr;
+        h.key_frame = 0; h.num_coeff_blocks = j.num_coeff_blocks;
+        h.num_intra_mbs = intra_mbs[i]; h.has_intra_mb = intra_mbs[i] != 0;
+        status[i] = aa_stream_append_records( j.stream, &h, j.mbs_out, j.coeffs_out, &j.frame_index );
+        if ( status[i] != AA_OK ) message[i] = g_last_error;
+      }
+    };
+    const int workers = std::max( 1, std::min( worker_threads( 0 ), n ) );
+    if ( workers == 1 ) work();
+    else {
+      std::vector<std::thread> pool;
+      for ( int t = 0; t < workers; t++ ) pool.emplace_back( work );
+      for ( auto & t : pool ) t.join();
+    }
+    for ( int i = 0; i < n; i++ ) if ( status[i] != AA_OK ) return fail( status[i], message[i] );
+  }
+  const double t_end = now_ms();
+  const double timing[5] = { t_end - t_call, ms_kernels, ms_download, ms_records, t_end - t_append };
+  std::memcpy( ctx->reencode_timing, timing, sizeof timing );
+  return AA_OK;
+}
+
+aa_status aa_reencode_last_timing( aa_ctx * ctx, double out[5] )
+{
+  if ( !ctx || !out ) return fail( AA_ERR_ARGUMENT, "aa_reencode_last_timing: null argument" );
+  std::memcpy( out, ctx->reencode_timing, sizeof ctx->reencode_timing );
+  return AA_OK;
+}
+
+} // extern "C"

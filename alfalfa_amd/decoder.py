@@ -355,6 +355,38 @@ class Context:
             cur.wait_stream(compute)
         return Quality(ssim, sse)
 
+    def _target_planes(self, what, i, d, t):
+        """targets[i] of a rebase / re-encode, checked -> (y, u, v) device tensors of decoder d's padded plane shapes."""
+        import torch
+        device = torch.device("cuda", self.device)
+        pw, ph = d.padded_width, d.padded_height
+        shapes = [(ph, pw), (ph // 2, pw // 2), (ph // 2, pw // 2)]
+        if isinstance(t, torch.Tensor):
+            if t.dtype != torch.uint8 or t.device != device or not t.is_contiguous() or t.numel() != pw * ph * 3 // 2:
+                raise ValueError("%s: targets[%d] must be a contiguous torch.uint8 tensor of %d bytes on %s" % (what, i, pw * ph * 3 // 2, device))
+            flat = t.reshape(-1)
+            t = (flat[:pw * ph].view(shapes[0]), flat[pw * ph:pw * ph * 5 // 4].view(shapes[1]), flat[pw * ph * 5 // 4:].view(shapes[2]))
+        if len(t) != 3:
+            raise ValueError("%s: targets[%d] must be a tensor or (y, u, v)" % (what, i))
+        for p, (pl, shape) in enumerate(zip(t, shapes)):
+            if tuple(pl.shape) != shape or pl.dtype != torch.uint8 or pl.device != device or pl.stride(1) != 1 or pl.stride(0) < shape[1]:
+                raise ValueError("%s: targets[%d]: plane %d must be torch.uint8 of shape %s on %s with contiguous rows" % (what, i, p, shape, device))
+        if t[1].stride(0) != t[2].stride(0):
+            raise ValueError("%s: targets[%d]: u and v must have the same row stride" % (what, i))
+        return t
+
+    @staticmethod
+    def _header_struct(header):
+        hdr = FrameHeader()
+        for name, _ in FrameHeader._fields_:
+            if name == "quant":
+                for sgm in range(4):
+                    for k in range(6):
+                        hdr.quant[sgm][k] = header["quant"][sgm][k]
+            else:
+                setattr(hdr, name, header[name])
+        return hdr
+
     def rebase(self, decoders, headers, mbs, targets):
         """The rebase (aa_rebase_batch; Encoder::update_residues, reencode.cc:236-303), one new frame per decoder: headers[i] (a dict
         as Parser.parse / frame_header return it: quant[0] are the factors divided by, key_frame 0) and mbs[i] (the prediction frame's
@@ -371,28 +403,8 @@ class Context:
         jobs = (capi.RebaseJob * n)()
         keep, outs = [], []
         for i, (d, header, mb, t) in enumerate(zip(decoders, headers, mbs, targets)):
-            pw, ph = d.padded_width, d.padded_height
-            shapes = [(ph, pw), (ph // 2, pw // 2), (ph // 2, pw // 2)]
-            if isinstance(t, torch.Tensor):
-                if t.dtype != torch.uint8 or t.device != device or not t.is_contiguous() or t.numel() != pw * ph * 3 // 2:
-                    raise ValueError("rebase: targets[%d] must be a contiguous torch.uint8 tensor of %d bytes on %s" % (i, pw * ph * 3 // 2, device))
-                flat = t.reshape(-1)
-                t = (flat[:pw * ph].view(shapes[0]), flat[pw * ph:pw * ph * 5 // 4].view(shapes[1]), flat[pw * ph * 5 // 4:].view(shapes[2]))
-            if len(t) != 3:
-                raise ValueError("rebase: targets[%d] must be a tensor or (y, u, v)" % i)
-            for p, (pl, shape) in enumerate(zip(t, shapes)):
-                if tuple(pl.shape) != shape or pl.dtype != torch.uint8 or pl.device != device or pl.stride(1) != 1 or pl.stride(0) < shape[1]:
-                    raise ValueError("rebase: targets[%d]: plane %d must be torch.uint8 of shape %s on %s with contiguous rows" % (i, p, shape, device))
-            if t[1].stride(0) != t[2].stride(0):
-                raise ValueError("rebase: targets[%d]: u and v must have the same row stride" % i)
-            hdr = FrameHeader()
-            for name, _ in FrameHeader._fields_:
-                if name == "quant":
-                    for sgm in range(4):
-                        for k in range(6):
-                            hdr.quant[sgm][k] = header["quant"][sgm][k]
-                else:
-                    setattr(hdr, name, header[name])
+            t = self._target_planes("rebase", i, d, t)
+            hdr = self._header_struct(header)
             nmb = hdr.mb_width * hdr.mb_height
             rec = np.ascontiguousarray(mb, dtype=MB_INFO_DTYPE).reshape(-1)
             if len(rec) != nmb:
@@ -415,6 +427,50 @@ class Context:
         out = (C.c_double * 5)()
         capi.check(self.L.aa_rebase_last_timing(self.h, out))
         return dict(zip(("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms"), out))
+
+    def reencode_as_inter(self, decoders, headers, targets, quality="best", append=True):
+        """The re-encode (aa_reencode_batch; Encoder::reencode_as_interframe, reencode.cc:38-129), one new frame per decoder: targets[i]
+        -- a chunk's first picture -- encoded as an inter frame predicted from decoders[i]'s current last reference, every macroblock's
+        mode chosen as the reference's encoder chooses it (quality: "best" or "rt", for all jobs or one per job).  headers[i] and
+        targets[i] as for rebase.  -> per job (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]) as rebase returns them; with append
+        False nothing is appended and frame_index is -1 (the records go through Decoder.append_records when the frame is final).
+        Synchronous."""
+        import torch
+        n = len(decoders)
+        if n == 0 or len(headers) != n or len(targets) != n:
+            raise ValueError("reencode_as_inter: need as many headers and targets as decoders, and at least one")
+        qualities = [quality] * n if isinstance(quality, str) else list(quality)
+        if len(qualities) != n or any(q not in ("best", "rt") for q in qualities):
+            raise ValueError("reencode_as_inter: quality is \"best\" or \"rt\", one for all jobs or one per job")
+        jobs = (capi.ReencodeJob * n)()
+        keep, outs = [], []
+        for i, (d, header, t) in enumerate(zip(decoders, headers, targets)):
+            t = self._target_planes("reencode_as_inter", i, d, t)
+            hdr = self._header_struct(header)
+            nmb = hdr.mb_width * hdr.mb_height
+            mb_out = np.zeros(nmb, dtype=MB_INFO_DTYPE)
+            cf = np.zeros((nmb * 25, 16), dtype=np.int16)
+            j = jobs[i]
+            j.stream, j.hdr = d.h, C.pointer(hdr)
+            j.target.y, j.target.u, j.target.v = t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr()
+            j.target.y_stride, j.target.uv_stride = t[0].stride(0), t[1].stride(0)
+            j.quality, j.append = (1 if qualities[i] == "rt" else 0), int(bool(append))
+            j.mbs_out, j.coeffs_out, j.coeff_capacity_blocks = mb_out.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p), len(cf)
+            keep.append((hdr, t))
+            outs.append((mb_out, cf, hdr.mb_width, hdr.mb_height))
+        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()      # (the targets are ready; the call itself waits for its kernel)
+        capi.check(self.L.aa_reencode_batch(self.h, jobs, n))
+        return [(jobs[i].frame_index, mb_out.reshape(mbh, mbw), cf[:jobs[i].num_coeff_blocks].copy()) for i, (mb_out, cf, mbw, mbh) in enumerate(outs)]
+
+    def reencode_timing(self):
+        """The last re-encode of this context (aa_reencode_last_timing), ms: call, upload + kernel, download, host records, append."""
+        out = (C.c_double * 5)()
+        capi.check(self.L.aa_reencode_last_timing(self.h, out))
+        return dict(zip(("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms"), out))
+
+    def set_reencode_slots(self, slots):
+        """Macroblocks of an anti-diagonal per round of the re-encode kernel (aa_ctx_set_reencode_slots: 1..16, default 16)."""
+        capi.check(self.L.aa_ctx_set_reencode_slots(self.h, int(slots)))
 
     def _hash_streams(self, what, decoders):
         n = len(decoders)
@@ -542,6 +598,10 @@ class Decoder:
     def rebase(self, header, mb, target):
         """One new frame of this decoder by rebase (Context.rebase) -> (frame_index, mb [mbh, mbw], coeff_blocks [n, 16])."""
         return self.ctx.rebase([self], [header], [mb], [target])[0]
+
+    def reencode_as_inter(self, header, target, quality="best", append=True):
+        """One new frame of this decoder by re-encode (Context.reencode_as_inter) -> (frame_index, mb [mbh, mbw], coeff_blocks [n, 16])."""
+        return self.ctx.reencode_as_inter([self], [header], [target], quality, append)[0]
 
     def upload(self):
         capi.check(self.L.aa_stream_upload(self.h))

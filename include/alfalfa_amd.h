@@ -498,6 +498,40 @@ aa_status aa_rebase_batch( aa_ctx * ctx, aa_rebase_job * jobs, int n );
  * and the two kernels, [2] coefficients and masks down (HIP events on the compute stream, summed over the call's slices); [3] the
  * records built on the host, [4] the frames appended (wall clock).  For tools/rebase_probe.py. */
 aa_status aa_rebase_last_timing( aa_ctx * ctx, double out[5] );
+
+/* The RE-ENCODE (Encoder::reencode_as_interframe, reencode.cc:38-129, the first thing xc-enc -r does to a chunk): the chunk's key frame
+ * is encoded again as an inter frame predicted from the references the stream holds NOW -- the frame that joins two chunks.  Per
+ * macroblock, in the reference's order and with its tie-breaks: the intra candidates (the B_PRED trial under AA_REENCODE_BEST, then
+ * TM, H, V, DC), then ZEROMV, NEARESTMV, NEARMV and NEWMV from the last reference (NEWMV by the reference's diamond search; under
+ * AA_REENCODE_REALTIME only where column % 4 == 0 and row % 4 == 0), the cheapest by its rate-distortion cost; then the chosen mode is
+ * applied as the rebase applies it (forward DCT / WHT, plain division, reconstruction; an intra macroblock's uv_mode by distortion
+ * alone).  One job = one (stream, new frame); jobs are independent, one workgroup each, one kernel on the compute stream.  The call
+ * is synchronous: it returns with the records in the caller's arrays -- what aa_parser_parse would make of the serialised frame
+ * (lf_level from hdr's level and the stream's current filter adjustments; segment_id 0; token probabilities, the loop-filter search
+ * and Frame::serialize stay with the caller) -- and, where `append` is set, the frame appended to its stream as aa_stream_append_records
+ * appends it: decode it with aa_decode_batch.  With `append` clear nothing is appended and frame_index is -1: for a caller who runs
+ * aa_stream_lf_search before the frame is final.  The vector costs come from the stream's current motion-vector probabilities.
+ * Errors as aa_rebase_batch's (AA_ERR_ARGUMENT unless noted; nothing is appended to any stream of the call): key_frame set;
+ * segmentation_enabled (AA_ERR_UNSUPPORTED, as the reference); null pointers; a header of another size; a stream listed twice; a stream
+ * with a frame appended but not decoded (AA_ERR_LOGIC); coeff_capacity_blocks too small (the message names the count needed). */
+#define AA_REENCODE_BEST 0
+#define AA_REENCODE_REALTIME 1
+typedef struct aa_reencode_job {
+  aa_stream * stream;          /* predicted from ITS last reference; the new frame is appended to it */
+  const aa_frame_header * hdr; /* header of the NEW frame, as aa_rebase_job's: quant[0][*], loop filter fields, refresh flags; key_frame must be 0 */
+  aa_quality_ref target;       /* DEVICE planes of the padded size, edge-extended by the caller */
+  int quality;                 /* AA_REENCODE_BEST / AA_REENCODE_REALTIME (xc-enc -q best / rt) */
+  int append;                  /* != 0: append the frame to the stream */
+  aa_mb_info * mbs_out; int16_t * coeffs_out; size_t coeff_capacity_blocks;   /* host */
+  uint32_t num_coeff_blocks; int frame_index;                                  /* out */
+} aa_reencode_job;
+aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n );
+/* As aa_rebase_last_timing, for the last successful aa_reencode_batch: [1] job table and rate models up and the kernel. */
+aa_status aa_reencode_last_timing( aa_ctx * ctx, double out[5] );
+/* How many macroblocks of an anti-diagonal a round of the re-encode kernel takes (1..16, default 16; also ALFALFA_AMD_REENC_SLOTS at
+ * context creation): with a small cap the several-rounds-per-diagonal path runs on a small frame (tests). */
+aa_status aa_ctx_set_reencode_slots( aa_ctx * ctx, int slots );
+
 /* Quantizer::Quantizer( QuantIndices ) (quantization.cc:83-93): out = {y_dc, y_ac, y2_dc, y2_ac, uv_dc, uv_ac} for the base index
  * y_ac_qi and the header's deltas {y_dc, y2_dc, y2_ac, uv_dc, uv_ac} (NULL: all zero) -- aa_frame_header::quant[0] of a new frame. */
 void aa_quant_factors( int y_ac_qi, const int8_t deltas[5], uint16_t out[6] );

@@ -827,6 +827,25 @@ public:
     return job.frame_index;
   }
 
+  // Encoder::reencode_as_interframe (reencode.cc:38-129; Encoder::reencode's option 1) for ONE new frame of this decoder
+  // (aa_reencode_batch with one job; many decoders at once: the C call): `target` -- the chunk's first picture, padded and edge-extended,
+  // in DEVICE memory -- encoded as an inter frame predicted from this decoder's current last reference, every macroblock's mode chosen as
+  // the reference's encoder chooses it (quality: AA_REENCODE_BEST / AA_REENCODE_REALTIME).  -> index of the frame appended to the
+  // stream, or -1 with append = false (run aa_stream_lf_search on the serialised frame first, then append the records).
+  int reencode_as_interframe( const aa_frame_header & header, const aa_quality_ref & target, const int quality,
+                              std::vector<aa_mb_info> & records_out, std::vector<int16_t> & coefficients_out, const bool append = true )
+  {
+    const size_t nmb = size_t( header.mb_width ) * header.mb_height;
+    records_out.resize( nmb ); coefficients_out.resize( nmb * 25 * 16 );
+    aa_reencode_job job;
+    std::memset( &job, 0, sizeof job );
+    job.stream = owner_->stream; job.hdr = &header; job.target = target; job.quality = quality; job.append = append;
+    job.mbs_out = records_out.data(); job.coeffs_out = coefficients_out.data(); job.coeff_capacity_blocks = nmb * 25;
+    check( aa_reencode_batch( owner_->ctx->get(), &job, 1 ) );
+    coefficients_out.resize( size_t( job.num_coeff_blocks ) * 16 );
+    return job.frame_index;
+  }
+
   static std::vector<std::pair<bool, RasterHandle>> get_frame_outputs( const std::vector<Decoder *> & decoders, const std::vector<Chunk> & frames )
   {
     if ( decoders.size() != frames.size() || decoders.empty() ) throw std::invalid_argument( "get_frame_outputs: one frame per decoder" );
