@@ -38,6 +38,44 @@ class FrameHeader(C.Structure):
         return d
 
 
+class FrameHeaderExt(C.Structure):
+    """aa_frame_header_ext: what the bitstream's frame header holds beyond FrameHeader (bytes only; arrays as nested lists in dicts)."""
+    _u8, _i8 = C.c_uint8, C.c_int8
+    _fields_ = [(n, C.c_uint8) for n in ("color_space", "clamping_type", "filter_type", "refresh_entropy_probs", "update_mb_segmentation_map",
+                                         "update_segment_feature_data", "segment_feature_mode", "lf_delta_update")] + [
+        ("seg_quant_update", _u8 * 4), ("seg_quant", _i8 * 4), ("seg_lf_update", _u8 * 4), ("seg_lf", _i8 * 4),
+        ("seg_tree_update", _u8 * 3), ("seg_tree_probs", _u8 * 3), ("skip_enabled", _u8), ("prob_skip_false", _u8),
+        ("ref_lf_update", _u8 * 4), ("ref_lf_delta", _i8 * 4), ("mode_lf_update", _u8 * 4), ("mode_lf_delta", _i8 * 4),
+        ("q_update", _u8 * 5), ("q_delta", _i8 * 5), ("prob_inter", _u8), ("prob_references_last", _u8), ("prob_references_golden", _u8),
+        ("intra_16x16_update", _u8), ("intra_16x16_prob", _u8 * 4), ("intra_chroma_update", _u8), ("intra_chroma_prob", _u8 * 3),
+        ("mv_prob_update", _u8 * 38), ("mv_prob", _u8 * 38), ("token_prob_update", _u8 * 1056), ("token_prob", _u8 * 1056)]
+
+    def as_dict(self):
+        """Scalars as ints, arrays as lists (mv_*: 38 = [2][19], token_*: 1056 = [4][8][3][11], flat)."""
+        return {n: (getattr(self, n) if isinstance(getattr(self, n), int) else list(getattr(self, n))) for n, _ in self._fields_}
+
+    @classmethod
+    def from_dict(cls, d):
+        x = cls()
+        for n, t in cls._fields_:
+            if n not in d:
+                continue
+            if hasattr(t, "_length_"):
+                v = [int(e) for e in np.asarray(d[n]).reshape(-1)]
+                if len(v) != t._length_:
+                    raise ValueError("FrameHeaderExt: %s holds %d values, not %d" % (n, len(v), t._length_))
+                setattr(x, n, t(*v))
+            else:
+                setattr(x, n, int(d[n]))
+        return x
+
+
+class SerializeJob(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("frame_index", C.c_int), ("hdr", C.POINTER(FrameHeader)), ("ext", C.POINTER(FrameHeaderExt)),
+                ("optimise", C.c_int), ("advance_state", C.c_int), ("probs_before", C.c_void_p), ("sub_modes", C.c_void_p), ("num_sub_modes", C.c_size_t), ("out", C.c_void_p), ("capacity", C.c_size_t),
+                ("size", C.c_size_t), ("counts_out", C.c_void_p)]
+
+
 class FrameIn(C.Structure):
     _fields_ = [("stream", C.c_void_p), ("data", C.c_char_p), ("size", C.c_size_t)]
 
@@ -153,6 +191,10 @@ SYMBOLS = [
     ("aa_reencode_batch", C.c_int, [_P, C.POINTER(ReencodeJob), C.c_int]),
     ("aa_reencode_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_ctx_set_reencode_slots", C.c_int, [_P, C.c_int]),
+    ("aa_parser_last_header_ext", C.c_int, [_P, C.POINTER(FrameHeaderExt)]), ("aa_stream_last_header_ext", C.c_int, [_P, C.POINTER(FrameHeaderExt)]),
+    ("aa_parser_last_sub_modes", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]), ("aa_stream_last_sub_modes", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("aa_serialize_host", C.c_int, [C.POINTER(FrameHeader), C.POINTER(FrameHeaderExt), _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("aa_serialize_batch", C.c_int, [_P, C.POINTER(SerializeJob), C.c_int]), ("aa_serialize_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_quant_factors", None, [C.c_int, C.POINTER(C.c_int8), C.POINTER(C.c_uint16)]),
     ("aa_stream_references", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("aa_stream_reference_slots", C.c_int, [_P, C.POINTER(C.c_int)]),

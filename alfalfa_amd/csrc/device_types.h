@@ -89,6 +89,27 @@ struct aa_reencode_dev_job {
   uint32_t * nb;               // [mbw * mbh][4]: aa::ReencNeighbour
 };
 
+// One (stream, frame) of a serialisation (aa_serialize_batch): the frame's records as reconstruction reads them, the tables its tokens are
+// coded with, and where the DCT partitions go: partition p owns [out + p * region, out + (p + 1) * region) and reports the bytes it takes
+// -- more than `region`: it did not fit, and what did not fit was not stored -- in sizes[p].
+struct aa_serialize_dev_job {
+  const aa_dev_frame * frame;
+  uint8_t * out;
+  uint32_t * sizes;            // [8]
+  uint32_t region;             // bytes per partition
+  uint32_t nparts;             // 1, 2, 4 or 8
+  uint32_t skip_enabled;       // the header has prob_skip_false: macroblocks flagged AA_MB_SKIP write no tokens
+  uint32_t optimise;           // the probability passes run first: k_token_counts fills `counts`, k_token_probs turns `probs` (the tables before
+                               // the frame) into the frame's tables and writes `updates`
+  uint32_t * counts;           // [AA_SERIALIZE_COUNTS]: branch counts [4][8][3][11][2] {false, true}, then macroblocks with coefficients and
+                               // macroblocks by reference frame (intra, last, golden, altref); zeroed by the host
+  uint8_t * updates;           // [AA_SERIALIZE_UPDATES]: 1056 update flags, 1056 values, then prob_skip_false, prob_inter, prob_references_last,
+                               // prob_references_golden as calc_prob gives them (0: no macroblock on the false side)
+  uint8_t probs[1056];         // [4][8][3][11]
+};
+#define AA_SERIALIZE_COUNTS ( 2112 + 8 )
+#define AA_SERIALIZE_UPDATES ( 2112 + 8 )
+
 #define AA_MAX_XCD 16
 
 #define AA_SYNC_WS_DUMP 140
@@ -184,4 +205,10 @@ int launch_rebase( const aa_rebase_dev_job * jobs, int n, uint32_t max_mbs, bool
 // reencode_kernels.hip: jobs[i] (n of them) -> records, dense coefficients, masks and the unfiltered reconstruction: k_reencode_inter, one
 // workgroup per job; slots: macroblocks of an anti-diagonal a round takes (1..16)
 int launch_reencode( const aa_reencode_dev_job * jobs, int n, int slots, void * stream );
+// serialize_kernels.hip: k_serialize_tokens, a lane per (job, DCT partition): lanes[i] = job << 3 | partition, n_lanes of them,
+// lanes_per_wave (1..64) to a wave
+int launch_serialize_tokens( const aa_serialize_dev_job * jobs, const uint32_t * lanes, int n_lanes, int lanes_per_wave, void * stream );
+// ... the probability passes in front of it, for the jobs (of n) that have `optimise` set: k_token_counts over runs of macroblocks x jobs
+// (max_mbs: the largest job's macroblocks), then k_token_probs, a thread per job and probability
+int launch_serialize_probs( aa_serialize_dev_job * jobs, int n, uint32_t max_mbs, void * stream );
 }

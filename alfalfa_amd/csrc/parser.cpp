@@ -289,8 +289,10 @@ void Parser::parse_header_impl( const uint8_t * data, size_t size, aa_frame_head
   hdr.num_macroblocks = mbw_ * mbh_;
   hdr.compressed_size = static_cast<uint32_t>( size );
 
+  aa_frame_header_ext x {};      // what aa_frame_header does not hold of the header (last_header_ext)
   bool color_space = false, clamping_type = false;
   if ( key ) { color_space = bd.flag(); clamping_type = bd.flag(); }
+  x.color_space = color_space; x.clamping_type = clamping_type;
 
   // Flagged<UpdateSegmentation>
   const bool seg_enabled = bd.flag();
@@ -302,11 +304,13 @@ void Parser::parse_header_impl( const uint8_t * data, size_t size, aa_frame_head
     seg_update_data = bd.flag();
     if ( seg_update_data ) {
       seg_abs = bd.flag();
-      for ( int i = 0; i < 4; i++ ) seg_quant[i] = bd.flag() ? bd.signed_literal( 7 ) : 0;
-      for ( int i = 0; i < 4; i++ ) seg_lf[i] = bd.flag() ? bd.signed_literal( 6 ) : 0;
+      for ( int i = 0; i < 4; i++ ) { seg_quant[i] = ( x.seg_quant_update[i] = bd.flag() ) ? bd.signed_literal( 7 ) : 0; x.seg_quant[i] = static_cast<int8_t>( seg_quant[i] ); }
+      for ( int i = 0; i < 4; i++ ) { seg_lf[i] = ( x.seg_lf_update[i] = bd.flag() ) ? bd.signed_literal( 6 ) : 0; x.seg_lf[i] = static_cast<int8_t>( seg_lf[i] ); }
     }
-    if ( seg_update_map ) for ( int i = 0; i < 3; i++ ) seg_tree_probs[i] = bd.flag() ? static_cast<uint8_t>( bd.literal( 8 ) ) : 255;
+    if ( seg_update_map ) for ( int i = 0; i < 3; i++ ) seg_tree_probs[i] = ( x.seg_tree_update[i] = bd.flag() ) ? static_cast<uint8_t>( bd.literal( 8 ) ) : 255;
   }
+  x.update_mb_segmentation_map = seg_update_map; x.update_segment_feature_data = seg_update_data; x.segment_feature_mode = seg_abs;
+  std::memcpy( x.seg_tree_probs, seg_tree_probs, 3 );
   const bool filter_type = bd.flag();
   hdr.loop_filter_level = static_cast<uint8_t>( bd.literal( 6 ) );
   hdr.sharpness_level = static_cast<uint8_t>( bd.literal( 3 ) );
@@ -317,16 +321,17 @@ void Parser::parse_header_impl( const uint8_t * data, size_t size, aa_frame_head
   if ( lf_adj_enabled ) {
     lf_delta_update = bd.flag();
     if ( lf_delta_update ) {
-      for ( int i = 0; i < 4; i++ ) ref_delta[i] = bd.flag() ? bd.signed_literal( 6 ) : 0;
-      for ( int i = 0; i < 4; i++ ) mode_delta[i] = bd.flag() ? bd.signed_literal( 6 ) : 0;
+      for ( int i = 0; i < 4; i++ ) { ref_delta[i] = ( x.ref_lf_update[i] = bd.flag() ) ? bd.signed_literal( 6 ) : 0; x.ref_lf_delta[i] = static_cast<int8_t>( ref_delta[i] ); }
+      for ( int i = 0; i < 4; i++ ) { mode_delta[i] = ( x.mode_lf_update[i] = bd.flag() ) ? bd.signed_literal( 6 ) : 0; x.mode_lf_delta[i] = static_cast<int8_t>( mode_delta[i] ); }
     }
   }
+  x.filter_type = filter_type; x.lf_delta_update = lf_delta_update;
   const int log2_parts = bd.literal( 2 );
   hdr.num_dct_partitions = static_cast<uint8_t>( 1 << log2_parts );
   const int y_ac_qi = bd.literal( 7 );
   hdr.q_index = static_cast<uint8_t>( y_ac_qi );
   int qdelta[5];   // y_dc, y2_dc, y2_ac, uv_dc, uv_ac (bitstream order, frame_header.hh:40-44)
-  for ( int i = 0; i < 5; i++ ) qdelta[i] = bd.flag() ? bd.signed_literal( 4 ) : 0;
+  for ( int i = 0; i < 5; i++ ) { qdelta[i] = ( x.q_update[i] = bd.flag() ) ? bd.signed_literal( 4 ) : 0; x.q_delta[i] = static_cast<int8_t>( qdelta[i] ); }
 
   bool refresh_entropy;
   bool sign_bias_golden = false, sign_bias_alt = false;
@@ -349,16 +354,18 @@ void Parser::parse_header_impl( const uint8_t * data, size_t size, aa_frame_head
   if ( key ) ft.set_defaults();   // key frames reset the persistent state (decoder.cc:234-240), applied below once the header is valid
   else ft = probs_;
   for ( int i = 0; i < 4; i++ ) for ( int j = 0; j < 8; j++ ) for ( int k = 0; k < 3; k++ ) for ( int l = 0; l < 11; l++ )
-    if ( bd.get( k_coeff_update_probs[( ( i * 8 + j ) * 3 + k ) * 11 + l] ) ) ft.coeff[i][j][k][l] = static_cast<uint8_t>( bd.literal( 8 ) );
+    if ( bd.get( k_coeff_update_probs[( ( i * 8 + j ) * 3 + k ) * 11 + l] ) ) { x.token_prob_update[i][j][k][l] = 1; x.token_prob[i][j][k][l] = ft.coeff[i][j][k][l] = static_cast<uint8_t>( bd.literal( 8 ) ); }
   const bool skip_enabled = bd.flag();
   const int prob_skip = skip_enabled ? bd.literal( 8 ) : 0;
+  x.refresh_entropy_probs = refresh_entropy; x.skip_enabled = skip_enabled; x.prob_skip_false = static_cast<uint8_t>( prob_skip );
   int prob_inter = 0, prob_last = 0, prob_golden = 0;
   if ( !key ) {
     prob_inter = bd.literal( 8 ); prob_last = bd.literal( 8 ); prob_golden = bd.literal( 8 );
-    if ( bd.flag() ) for ( int i = 0; i < 4; i++ ) ft.y_mode[i] = static_cast<uint8_t>( bd.literal( 8 ) );
-    if ( bd.flag() ) for ( int i = 0; i < 3; i++ ) ft.uv_mode[i] = static_cast<uint8_t>( bd.literal( 8 ) );
+    if ( ( x.intra_16x16_update = bd.flag() ) ) for ( int i = 0; i < 4; i++ ) x.intra_16x16_prob[i] = ft.y_mode[i] = static_cast<uint8_t>( bd.literal( 8 ) );
+    if ( ( x.intra_chroma_update = bd.flag() ) ) for ( int i = 0; i < 3; i++ ) x.intra_chroma_prob[i] = ft.uv_mode[i] = static_cast<uint8_t>( bd.literal( 8 ) );
     for ( int i = 0; i < 2; i++ ) for ( int j = 0; j < 19; j++ )
-      if ( bd.get( k_mv_update_probs[i * 19 + j] ) ) { const int x = bd.literal( 7 ); ft.mv[i][j] = static_cast<uint8_t>( x ? x << 1 : 1 ); }
+      if ( bd.get( k_mv_update_probs[i * 19 + j] ) ) { const int v = bd.literal( 7 ); x.mv_prob_update[i][j] = 1; x.mv_prob[i][j] = static_cast<uint8_t>( v ); ft.mv[i][j] = static_cast<uint8_t>( v ? v << 1 : 1 ); }
+    x.prob_inter = static_cast<uint8_t>( prob_inter ); x.prob_references_last = static_cast<uint8_t>( prob_last ); x.prob_references_golden = static_cast<uint8_t>( prob_golden );
   }
   if ( color_space || clamping_type ) throw ParseError( AA_ERR_UNSUPPORTED, "unsupported bitstream: VP8 color_space and clamping_type bits" );
   if ( filter_type ) throw ParseError( AA_ERR_UNSUPPORTED, "unsupported bitstream: VP8 'simple' in-loop deblocking filter" );
@@ -433,6 +440,7 @@ void Parser::parse_header_impl( const uint8_t * data, size_t size, aa_frame_head
   std::memcpy( fp.y_mode_probs, ft.y_mode, 4 ); std::memcpy( fp.uv_mode_probs, ft.uv_mode, 3 ); std::memcpy( fp.mv_probs, ft.mv, 38 );
   std::memcpy( fp.coeff_probs, ft.coeff, sizeof ft.coeff );
   seg_map_reset_ = seg_reset;
+  ext_ = x;
 }
 
 // Everything of a frame behind its header: macroblock headers (first partition, `bd` continuing behind the frame header) and
@@ -506,12 +514,31 @@ static void parse_body( BD & bd, const uint8_t * data, const FrameParams & fp, a
   coeff_blocks_out = coeff_blocks; intra_mbs_out = intra_mbs;
 }
 
+namespace {
+// The first partition's decoder with a tap on one tree: the sub-block modes of SPLITMV macroblocks (LEFT4X4 .. NEW4X4) in the order they
+// are read.  A record keeps the vector a mode produced, not the mode; a serialiser that is to write the frame's own bytes back needs it
+// (serializer.hh).
+struct SubModeTap {
+  BoolReader & r;
+  std::vector<uint8_t> & log;
+  int get( const uint32_t prob ) { return r.get( prob ); }
+  int tree( const int8_t * nodes, const uint8_t * probs )
+  {
+    const int v = r.tree( nodes, probs );
+    if ( nodes == kHeaderTables.sub_mv_ref_tree ) log.push_back( static_cast<uint8_t>( v ) );
+    return v;
+  }
+};
+}
+
 void Parser::parse( const uint8_t * data, size_t size, aa_frame_header & hdr, aa_mb_info * mbs, int16_t * coeff_out )
 {
   FrameParams fp;
-  BoolReader bd;                 // the first partition's decoder continues right behind the frame header
-  parse_header_impl( data, size, hdr, fp, bd );
+  BoolReader reader;             // the first partition's decoder continues right behind the frame header
+  parse_header_impl( data, size, hdr, fp, reader );
   uint32_t coeff_blocks = 0, intra_mbs = 0;
+  sub_modes_.clear();
+  SubModeTap bd { reader, sub_modes_ };
   parse_body( bd, data, fp, mbs, coeff_out, seg_.enabled ? seg_.map.data() : nullptr, above_nz_.data(), coeff_blocks, intra_mbs );
   hdr.num_coeff_blocks = coeff_blocks;
   hdr.num_intra_mbs = intra_mbs;

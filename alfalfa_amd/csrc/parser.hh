@@ -104,6 +104,11 @@ public:
   const ProbTables & probs() const { return probs_; }
   const SegmentationState & segmentation() const { return seg_; }
   const FilterAdjustState & filter_adjustments() const { return fadj_; }
+  // the header fields of the frame parsed last that aa_frame_header does not hold (what a serialiser writes back: serializer.hh)
+  const aa_frame_header_ext & last_header_ext() const { return ext_; }
+  // ... and what its records do not hold: the sub-block mode (LEFT4X4 .. NEW4X4) of every partition of every SPLITMV macroblock, in
+  // bitstream order (filled by parse(), not by the header pre-pass)
+  const std::vector<uint8_t> & last_sub_modes() const { return sub_modes_; }
 
 private:
   void parse_header_impl( const uint8_t * data, size_t size, aa_frame_header & hdr, FrameParams & fp, class BoolReader & bd );
@@ -114,6 +119,8 @@ private:
   ProbTables probs_;
   SegmentationState seg_;
   FilterAdjustState fadj_;
+  aa_frame_header_ext ext_ {};
+  std::vector<uint8_t> sub_modes_;
   std::vector<uint8_t> above_nz_;   // per MB column: 4 Y, 2 U, 2 V, 1 Y2
 };
 

@@ -42,8 +42,9 @@
 #include "coeff_pack.hh"
 #include "hash_chain.hh"
 #include "reencode_search.hh"
+#include "serializer.hh"
 
-// ONE translation unit, this file and the thirteen it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
+// ONE translation unit, this file and the fourteen it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
 // the pieces share file-local state (the anonymous-namespace helpers, g_last_error) and are #included in dependency order.
 #include "runtime_types.inc"
 #include "runtime_pool.inc"
@@ -58,3 +59,4 @@
 #include "runtime_lf_search.inc"
 #include "runtime_rebase.inc"
 #include "runtime_reencode.inc"
+#include "runtime_serialize.inc"

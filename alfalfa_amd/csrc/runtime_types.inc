@@ -229,6 +229,7 @@ struct aa_ctx {
   JobRing rgb_ring, quality_ring;
   double rebase_timing[5] = {};             // aa_rebase_last_timing
   double reencode_timing[5] = {};           // aa_reencode_last_timing
+  double serialize_timing[5] = {};          // aa_serialize_last_timing
   int reenc_slots = 16;                     // macroblocks of an anti-diagonal per round of k_reencode_inter (aa_ctx_set_reencode_slots)
   JobRing rebase_ring;                      // the job table and input records of a rebase slice (aa_rebase_batch), copied on the compute stream into the slice's piece
   hipEvent_t rgb_consumer_ev = nullptr, quality_consumer_ev = nullptr;   // stream_waits_for: the caller's stream and the compute stream waiting for each other

@@ -43,6 +43,22 @@ class Parser:
         h = hdr.as_dict()
         return h, self._mb.copy().reshape(self.mbh, self.mbw), self._coeff[:h["num_coeff_blocks"] * 16].copy().reshape(-1, 16)
 
+    def header_ext(self):
+        """The rest of the header of the frame parsed last (aa_parser_last_header_ext) -> dict of the fields of aa_frame_header_ext:
+        with the header dict of parse() it is everything a serialiser writes (Context.serialize_frames)."""
+        x = capi.FrameHeaderExt()
+        capi.check(self.L.aa_parser_last_header_ext(self.h, C.byref(x)))
+        return x.as_dict()
+
+    def sub_modes(self):
+        """The sub-block modes (10 LEFT4X4 .. 13 NEW4X4) of the SPLITMV partitions of the frame parsed last, in bitstream order
+        (aa_parser_last_sub_modes) -> uint8 array: what the records do not hold and a byte-exact serialisation needs."""
+        n = C.c_size_t()
+        capi.check(self.L.aa_parser_last_sub_modes(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), dtype=np.uint8)
+        capi.check(self.L.aa_parser_last_sub_modes(self.h, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)))
+        return out[:n.value]
+
     def set_error_concealment(self, on):
         """Decoder::set_error_concealment (decoder.hh:298): accept frames that end early."""
         capi.check(self.L.aa_parser_set_error_concealment(self.h, int(on)))
@@ -90,6 +106,25 @@ class Parser:
         en = C.c_int(); r, m = (C.c_int8 * 4)(), (C.c_int8 * 4)()
         capi.check(self.L.aa_parser_get_filter_adjustments(self.h, C.byref(en), r, m))
         return {"enabled": bool(en.value), "ref": list(r), "mode": list(m)}
+
+
+def serialize_host(header, ext, probs_before, mb, coeff_blocks, sub_modes=None, capacity=None):
+    """A frame given as records written as VP8 bytes by one host core (aa_serialize_host: the statements of the GPU's token lanes and the
+    host half's first partition; no device).  Arguments as Parser.parse / Parser.header_ext / Parser.probs / Parser.sub_modes return them."""
+    L = capi.lib()
+    hdr = Context._header_struct(header)
+    x = capi.FrameHeaderExt.from_dict(ext)
+    mbs = np.ascontiguousarray(mb, dtype=MB_INFO_DTYPE).reshape(-1)
+    cf = np.ascontiguousarray(coeff_blocks, dtype=np.int16).reshape(-1, 16)
+    hdr.num_coeff_blocks = len(cf)
+    pb = np.ascontiguousarray(probs_before, dtype=np.uint8).reshape(-1)
+    sm = None if sub_modes is None or len(sub_modes) == 0 else np.ascontiguousarray(sub_modes, dtype=np.uint8).reshape(-1)
+    cap = int(capacity) if capacity is not None else 4096 + len(mbs) * 768
+    out = np.zeros(cap, dtype=np.uint8)
+    size = C.c_size_t()
+    capi.check(L.aa_serialize_host(C.byref(hdr), C.byref(x), pb.ctypes.data_as(C.c_void_p), mbs.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p),
+                                   None if sm is None else sm.ctypes.data_as(C.c_void_p), 0 if sm is None else len(sm), out.ctypes.data_as(C.c_void_p), cap, C.byref(size)))
+    return out[:size.value].tobytes()
 
 
 class Context:
@@ -462,6 +497,63 @@ class Context:
         capi.check(self.L.aa_reencode_batch(self.h, jobs, n))
         return [(jobs[i].frame_index, mb_out.reshape(mbh, mbw), cf[:jobs[i].num_coeff_blocks].copy()) for i, (mb_out, cf, mbw, mbh) in enumerate(outs)]
 
+    def serialize_frames(self, decoders, frame_indices, headers, exts, probs_before=None, advance_state=False, capacity=None, optimise=False, sub_modes=None, details=False):
+        """The serialisation (aa_serialize_batch; Frame::serialize, serializer.cc:388-829): frame frame_indices[i] of decoders[i], held as
+        records (parsed, rebased, re-encoded or appended), written as a VP8 frame with the header headers[i] (a dict as Parser.parse /
+        frame_header return it) and exts[i] (a dict as Parser.header_ext returns it) -- DCT partitions on the GPU, first partition on the
+        host.  probs_before: per job 1101 bytes as Parser.probs() returns them, or None for the decoder's current tables (None for all:
+        every job); advance_state (one flag or one per job): the decoder's DecoderState then follows the written frame as if it had
+        parsed it.  capacity: bytes per frame (default: 4 KiB + 768 bytes per macroblock, twice a raw frame; a frame
+        that takes more is refused with the size it needs in the message).  sub_modes: per job None or the
+        SPLITMV sub-block modes of the frame the records came from (Parser.sub_modes): without them the frame parses to the same records
+        but is not necessarily the original's bytes.  optimise: the reference's probability passes (optimize_prob_skip,
+        optimize_interframe_probs, optimize_probability_tables) run on the GPU first and decide prob_skip_false, the three reference
+        probabilities and the token probability updates, whatever exts[i] says of them.  -> [bytes], or with details [(bytes, the
+        header extension as written, the branch counts the passes used: uint32 [2120], None without optimise)].  Synchronous.
+        (Decoder.serialize is the decoder's STATE in the reference's format; this is a frame.)"""
+        n = len(decoders)
+        if n == 0 or len(frame_indices) != n or len(headers) != n or len(exts) != n:
+            raise ValueError("serialize_frames: need as many frame indices, headers and header extensions as decoders, and at least one")
+        before = list(probs_before) if probs_before is not None else [None] * n
+        advance = list(advance_state) if isinstance(advance_state, (list, tuple)) else [advance_state] * n
+        caps = list(capacity) if isinstance(capacity, (list, tuple)) else [capacity] * n
+        subs = list(sub_modes) if sub_modes is not None else [None] * n
+        if len(before) != n or len(advance) != n or len(caps) != n or len(subs) != n:
+            raise ValueError("serialize_frames: per-job arguments must be one per decoder")
+        jobs = (capi.SerializeJob * n)()
+        keep, outs = [], []
+        for i, d in enumerate(decoders):
+            hdr = self._header_struct(headers[i])
+            ext = capi.FrameHeaderExt.from_dict(exts[i])
+            nmb = hdr.mb_width * hdr.mb_height
+            cap = int(caps[i]) if caps[i] is not None else 4096 + nmb * 768
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            pb = None if before[i] is None else np.ascontiguousarray(before[i], dtype=np.uint8).reshape(-1)
+            if pb is not None and len(pb) != 1101:
+                raise ValueError("serialize_frames: probs_before[%d] holds %d bytes, not 1101" % (i, len(pb)))
+            j = jobs[i]
+            j.stream, j.frame_index, j.hdr, j.ext = d.h, int(frame_indices[i]), C.pointer(hdr), C.pointer(ext)
+            j.optimise, j.advance_state = int(bool(optimise)), int(bool(advance[i]))
+            j.probs_before = None if pb is None else pb.ctypes.data_as(C.c_void_p)
+            j.out, j.capacity = out.ctypes.data_as(C.c_void_p), cap
+            sm = None if subs[i] is None or len(subs[i]) == 0 else np.ascontiguousarray(subs[i], dtype=np.uint8).reshape(-1)
+            j.sub_modes, j.num_sub_modes = (None, 0) if sm is None else (sm.ctypes.data_as(C.c_void_p), len(sm))
+            cnt = np.zeros(2120, dtype=np.uint32) if (optimise and details) else None
+            j.counts_out = None if cnt is None else cnt.ctypes.data_as(C.c_void_p)
+            keep.append((hdr, ext, pb, sm, cnt))
+            outs.append(out)
+        capi.check(self.L.aa_serialize_batch(self.h, jobs, n))
+        if details:
+            return [(outs[i][:jobs[i].size].tobytes(), keep[i][1].as_dict(), keep[i][4]) for i in range(n)]
+        return [outs[i][:jobs[i].size].tobytes() for i in range(n)]
+
+    def serialize_timing(self):
+        """The last serialisation of this context (aa_serialize_last_timing), ms: call, upload + token kernel, sizes + partitions down,
+        host first partitions (beside the kernel), assembly + copy + state advance."""
+        out = (C.c_double * 5)()
+        capi.check(self.L.aa_serialize_last_timing(self.h, out))
+        return dict(zip(("call_ms", "kernel_ms", "download_ms", "first_partition_ms", "assemble_ms"), out))
+
     def reencode_timing(self):
         """The last re-encode of this context (aa_reencode_last_timing), ms: call, upload + kernel, download, host records, append."""
         out = (C.c_double * 5)()
@@ -602,6 +694,17 @@ class Decoder:
     def reencode_as_inter(self, header, target, quality="best", append=True):
         """One new frame of this decoder by re-encode (Context.reencode_as_inter) -> (frame_index, mb [mbh, mbw], coeff_blocks [n, 16])."""
         return self.ctx.reencode_as_inter([self], [header], [target], quality, append)[0]
+
+    def serialize_frame(self, frame_index, header, ext, probs_before=None, advance_state=False, capacity=None, sub_modes=None, optimise=False, details=False):
+        """One frame of this decoder, held as records, as VP8 bytes (Context.serialize_frames)."""
+        return self.ctx.serialize_frames([self], [frame_index], [header], [ext], None if probs_before is None else [probs_before], advance_state, capacity,
+                                         optimise=optimise, sub_modes=None if sub_modes is None else [sub_modes], details=details)[0]
+
+    def header_ext(self):
+        """Parser.header_ext for this decoder's own parser: the frame parse_frame / get_frame_output / submit_frames parsed last."""
+        x = capi.FrameHeaderExt()
+        capi.check(self.L.aa_stream_last_header_ext(self.h, C.byref(x)))
+        return x.as_dict()
 
     def upload(self):
         capi.check(self.L.aa_stream_upload(self.h))

@@ -28,7 +28,11 @@ extern "C" {
 
 /* 4 (round 5): aa_ctx_info and aa_kernel_stats grew in round 4 (a caller built against version 3 passes smaller structs: check
  * aa_abi_version() against the header you compiled with before calling aa_ctx_get_info / aa_ctx_kernel_stats), packed coefficient
- * storage became the default, AA_SUBMIT_HOST on a big call no longer waits for the parse (host lanes), hand-overs are refused at the memory limit. */
+ * storage became the default, AA_SUBMIT_HOST on a big call no longer waits for the parse (host lanes), hand-overs are refused at the memory limit.
+ * Still 4 with the serialisation (aa_frame_header_ext, aa_parser_last_header_ext / aa_stream_last_header_ext, aa_parser_last_sub_modes /
+ * aa_stream_last_sub_modes, aa_serialize_batch, aa_serialize_last_timing): those are additions -- new entry points and new structs, no
+ * existing struct, enum or call changed -- so a caller built against version 4 is served as before; a caller that wants them asks the
+ * library for the symbols (dlsym / the bindings' symbol table), as tests/test_serialize_abi.py does. */
 #define AA_ABI_VERSION 4
 
 typedef enum aa_status {
@@ -111,6 +115,31 @@ typedef struct aa_frame_header {
   uint32_t compressed_size;
 } aa_frame_header;
 
+/* What the frame header of the bitstream holds beyond aa_frame_header (frame_header.hh:194-295): the fields a decoder consumes while it
+ * parses and a serialiser has to write (serializer.cc:110-181).  A `*_update[i]` byte says that the Flagged<> entry is present; the value
+ * beside it is what the bitstream holds (zero when absent).  aa_parser_last_header_ext / aa_stream_last_header_ext return the struct of
+ * the frame just parsed; aa_serialize_batch takes one per job.  Layout is ABI (bytes only). */
+typedef struct aa_frame_header_ext {
+  uint8_t color_space, clamping_type;                    /* key frames (the decoder refuses a frame that sets either) */
+  uint8_t filter_type;                                   /* 1: the 'simple' loop filter (refused by the decoder) */
+  uint8_t refresh_entropy_probs;
+  /* UpdateSegmentation (present when aa_frame_header::segmentation_enabled) */
+  uint8_t update_mb_segmentation_map, update_segment_feature_data, segment_feature_mode /* 1: absolute values */;
+  uint8_t lf_delta_update;                               /* ModeRefLFDeltaUpdate present (with filter_adjustments_enabled) */
+  uint8_t seg_quant_update[4]; int8_t seg_quant[4];      /* quantizer_update: 7 bits + sign */
+  uint8_t seg_lf_update[4]; int8_t seg_lf[4];            /* loop_filter_update: 6 bits + sign */
+  uint8_t seg_tree_update[3], seg_tree_probs[3];         /* mb_segmentation_map (with update_mb_segmentation_map); absent = 255 */
+  uint8_t skip_enabled, prob_skip_false;                 /* Flagged prob_skip_false */
+  uint8_t ref_lf_update[4]; int8_t ref_lf_delta[4];      /* ref_update: 6 bits + sign */
+  uint8_t mode_lf_update[4]; int8_t mode_lf_delta[4];    /* mode_update */
+  uint8_t q_update[5]; int8_t q_delta[5];                /* y_dc, y2_dc, y2_ac, uv_dc, uv_ac: 4 bits + sign */
+  uint8_t prob_inter, prob_references_last, prob_references_golden;   /* inter frames */
+  uint8_t intra_16x16_update, intra_16x16_prob[4];
+  uint8_t intra_chroma_update, intra_chroma_prob[3];
+  uint8_t mv_prob_update[2][19], mv_prob[2][19];         /* the 7 bits written: the table entry becomes x ? x << 1 : 1 */
+  uint8_t token_prob_update[4][8][3][11], token_prob[4][8][3][11];
+} aa_frame_header_ext;
+
 /* ------------------------------------------------------------------------------------------------
  * Host parser: the reference's DecoderState + parse_frame (decoder_state.hh:72-167).  Host only.
  * ---------------------------------------------------------------------------------------------- */
@@ -130,6 +159,13 @@ aa_status aa_parser_parse( aa_parser * p, const uint8_t * data, size_t size,
  * uncompressed_chunk.cc:34-130) -- what is there of the first partition is used, decoders read zeros past the end, a frame
  * without a complete tag becomes an inter frame of no bytes -- instead of AA_ERR_INVALID.  Off by default, as in the reference. */
 aa_status aa_parser_set_error_concealment( aa_parser * p, int on );
+/* The rest of the header of the frame this parser parsed last (aa_parser_parse; all zero before the first). */
+aa_status aa_parser_last_header_ext( const aa_parser * p, aa_frame_header_ext * out );
+/* ... and what its records do not hold: a SPLITMV macroblock's record has every partition's VECTOR, not the sub-block mode (10 LEFT4X4, 11
+ * ABOVE4X4, 12 ZERO4X4, 13 NEW4X4) that said it.  out[0 .. *count): the modes of the frame parsed last, partition after partition in bitstream
+ * order; out may be NULL (count only); more than `capacity` entries: AA_ERR_ARGUMENT, *count still set.  A serialiser that is to write the
+ * frame's own bytes back needs them (aa_serialize_job::sub_modes). */
+aa_status aa_parser_last_sub_modes( const aa_parser * p, uint8_t * out, size_t capacity, size_t * count );
 /* UncompressedChunk( frame, expected_width, expected_height, accept_partial ) (uncompressed_chunk.cc:34-130): what the frame tag
  * says, with the reference's checks and error classes.  corruption_level: 0 NO_CORRUPTION, 2 CORRUPTED_FIRST_PARTITION,
  * 3 CORRUPTED_FRAME (uncompressed_chunk.hh:40-46).  Any out pointer may be NULL. */
@@ -477,8 +513,8 @@ aa_status aa_stream_lf_search( aa_stream * s, const uint8_t * data, size_t size,
  * where a Y2 block is coded), plain division by the new header's factors, reconstruct (intra macroblocks predict from the new
  * frame's own unfiltered reconstruction).  One job = one (stream, new frame); jobs are independent and run as one pair of kernels on
  * the compute stream.  The call is synchronous: it returns with the records in the caller's arrays -- what aa_parser_parse would make
- * of the serialised frame (token probabilities and Frame::serialize stay with the caller) -- and the frame appended to its stream as
- * aa_stream_append_records appends it: decode it with aa_decode_batch like any other frame (the stream's DecoderState is not advanced).
+ * of the serialised frame (the choice of the token probabilities stays with the caller; Frame::serialize is aa_serialize_batch) -- and the
+ * frame appended to its stream as aa_stream_append_records appends it: decode it with aa_decode_batch like any other frame (the stream's DecoderState is not advanced).
  * Errors (AA_ERR_ARGUMENT unless noted; nothing is appended to any stream of the call): key_frame set; segmentation_enabled
  * (AA_ERR_UNSUPPORTED: the reference quantises with the frame quantiser whatever the segment); null pointers; a header of another size;
  * a stream listed twice; a stream with a frame appended but not decoded (AA_ERR_LOGIC); coeff_capacity_blocks too small (the message
@@ -507,8 +543,8 @@ aa_status aa_rebase_last_timing( aa_ctx * ctx, double out[5] );
  * applied as the rebase applies it (forward DCT / WHT, plain division, reconstruction; an intra macroblock's uv_mode by distortion
  * alone).  One job = one (stream, new frame); jobs are independent, one workgroup each, one kernel on the compute stream.  The call
  * is synchronous: it returns with the records in the caller's arrays -- what aa_parser_parse would make of the serialised frame
- * (lf_level from hdr's level and the stream's current filter adjustments; segment_id 0; token probabilities, the loop-filter search
- * and Frame::serialize stay with the caller) -- and, where `append` is set, the frame appended to its stream as aa_stream_append_records
+ * (lf_level from hdr's level and the stream's current filter adjustments; segment_id 0; the choice of the token probabilities and the
+ * loop-filter search stay with the caller; Frame::serialize is aa_serialize_batch) -- and, where `append` is set, the frame appended to its stream as aa_stream_append_records
  * appends it: decode it with aa_decode_batch.  With `append` clear nothing is appended and frame_index is -1: for a caller who runs
  * aa_stream_lf_search before the frame is final.  The vector costs come from the stream's current motion-vector probabilities.
  * Errors as aa_rebase_batch's (AA_ERR_ARGUMENT unless noted; nothing is appended to any stream of the call): key_frame set;
@@ -531,6 +567,68 @@ aa_status aa_reencode_last_timing( aa_ctx * ctx, double out[5] );
 /* How many macroblocks of an anti-diagonal a round of the re-encode kernel takes (1..16, default 16; also ALFALFA_AMD_REENC_SLOTS at
  * context creation): with a small cap the several-rounds-per-diagonal path runs on a small frame (tests). */
 aa_status aa_ctx_set_reencode_slots( aa_ctx * ctx, int slots );
+
+/* SERIALISATION (Frame::serialize, serializer.cc:388-829): frame `frame_index` of `stream`, held as records -- parsed from bytes, or appended
+ * by aa_rebase_batch / aa_reencode_batch / aa_stream_append_records -- becomes a VP8 frame in `out`.  The DCT partitions are written on the
+ * device from the records where they lie, dense or packed (k_serialize_tokens: a lane per job and partition, partition p takes the
+ * macroblock rows r % num_dct_partitions == p); meanwhile host workers, one job each, write the frame header and the macroblock headers of
+ * the first partition from the macroblock records (the same boolean encoder, bool_writer.hh) and then put the frame together: tag, key-frame
+ * start code and size, first partition, partition lengths, partitions.  What crosses the bus is the macroblock records (unless the host
+ * still has them) and the compressed partitions.
+ *   hdr           key_frame, show_frame, loop_filter_level, sharpness_level, num_dct_partitions, q_index, the refresh / copy / sign-bias flags,
+ *                 segmentation_enabled and filter_adjustments_enabled (the header's Flagged<> bits) are written; mb_width / mb_height must be
+ *                 the stream's.  num_dct_partitions need not be what the frame was parsed with.
+ *   ext           the rest of the header, written as given (aa_parser_last_header_ext of a parse is a complete one).
+ *   sub_modes     the sub-block modes of the SPLITMV macroblocks' partitions as aa_parser_last_sub_modes gives them for the frame the records
+ *                 came from (for a rebased frame: its prediction frame, whose modes the rebase keeps), or NULL.  A listed mode is written where
+ *                 it gives the record's vector; otherwise, and beyond the list, the first of LEFT4X4, ABOVE4X4, ZERO4X4 that gives the vector
+ *                 is, else NEW4X4.  Every choice parses back to the same records; only the listed one is the original frame's bytes.
+ *   probs_before  1101 bytes as aa_parser_get_probs returns them: the tables the frame's updates apply to (a key frame starts from the
+ *                 defaults whatever they are); NULL: the stream's current tables.
+ *   advance_state only with probs_before == NULL: afterwards the stream's DecoderState is advanced exactly as parsing the written frame
+ *                 advances it (probabilities under refresh_entropy_probs, segmentation and its map, filter adjustments) -- a chain of frames is
+ *                 then coded frame after frame against the state its predecessor left; hence a stream appears once per call.
+ *   optimise      the reference's probability passes run on the device first (k_token_counts, k_token_probs) and overwrite the fields of
+ *                 `ext` they decide: optimize_prob_skip (encoder.cc:442-457: skip_enabled 1, prob_skip_false), optimize_interframe_probs
+ *                 (encode_inter.cc:525-575: prob_inter, prob_references_last, prob_references_golden, each only where calc_prob gives > 0;
+ *                 inter frames) and optimize_probability_tables (encoder.cc:419-439: token_prob_update / token_prob, whatever the caller
+ *                 put there), with calc_prob (encoder.cc:48-55) as written: 256 * false / total in integers, 0 when nothing was false,
+ *                 an update where prob > 0 && prob != the table before the frame.  Counted are the Y, U and V blocks of EVERY macroblock
+ *                 (Y2 blocks are not: serializer.cc:582-586).  On success `ext` holds the header as it was written.  Clear: as given.
+ *   counts_out    optimise only, may be NULL: the counts the passes used, 2120 words: [4][8][3][11][2] {false, true}, then macroblocks with
+ *                 coefficients, macroblocks by reference frame (intra, last, golden, altref), three zeros.  For tests.
+ *   out, capacity host memory; size (out): the frame's bytes.  Nothing is written beyond capacity, on the host or in the device staging.
+ * Records must be what a parse produces: nz_mask bit b set exactly when block b holds a coefficient the tokens code (a Y block beside a Y2
+ * block from position 1 on), AA_MB_SKIP only with an empty nz_mask.  The call is synchronous.
+ * Refusals (AA_ERR_ARGUMENT unless noted; nothing is written to any `out` and no state is advanced for any job of a refused call): null
+ * pointers; a stream of another context or listed twice; frame_index out of range or released; num_dct_partitions not 1, 2, 4
+ * or 8; advance_state together with probs_before; a header of another size, a key frame that holds inter macroblocks; a frame that does not fit its capacity (the message names the job and the bytes needed). */
+typedef struct aa_serialize_job {
+  aa_stream * stream; int frame_index;
+  const aa_frame_header * hdr;
+  aa_frame_header_ext * ext;
+  int optimise, advance_state;
+  const uint8_t * probs_before;
+  const uint8_t * sub_modes; size_t num_sub_modes;
+  uint8_t * out; size_t capacity;
+  size_t size;                     /* out */
+  uint32_t * counts_out;
+} aa_serialize_job;
+aa_status aa_serialize_batch( aa_ctx * ctx, aa_serialize_job * jobs, int n );
+/* Where the last successful aa_serialize_batch spent its time, ms: out[0] the whole call (wall clock); [1] job table up and k_serialize_tokens,
+ * [2] partition sizes and partitions down (HIP events on the compute stream); [3] the host workers' frame headers and first partitions,
+ * [4] assembly, the copy into `out` and the state advance (wall clock; [3] runs beside [1]).  For tools/serialize_probe.py. */
+aa_status aa_serialize_last_timing( aa_ctx * ctx, double out[5] );
+/* The same frame written by ONE host core from records in host memory (what aa_parser_parse / aa_stream_read_records / aa_rebase_batch
+ * return: coeffs = dense blocks, a macroblock's at coeff_index): the host half's first partition and the token lanes' own statements
+ * (serialize_common.hh) run on the host.  No device, no context; `optimise` is not offered here.  For tools/serialize_probe.py (the chain
+ * on a host core beside the chain on a GPU lane) and for callers without a GPU at hand; it is no fallback of aa_serialize_batch, which
+ * never calls it.  *size: the frame's bytes; more than capacity: AA_ERR_ARGUMENT, nothing written. */
+aa_status aa_serialize_host( const aa_frame_header * hdr, const aa_frame_header_ext * ext, const uint8_t * probs_before, const aa_mb_info * mbs,
+                             const int16_t * coeffs, const uint8_t * sub_modes, size_t num_sub_modes, uint8_t * out, size_t capacity, size_t * size );
+/* aa_parser_last_header_ext for a stream's own parser: the frame aa_stream_parse / aa_stream_decode / aa_submit_frames parsed last. */
+aa_status aa_stream_last_header_ext( const aa_stream * s, aa_frame_header_ext * out );
+aa_status aa_stream_last_sub_modes( const aa_stream * s, uint8_t * out, size_t capacity, size_t * count );   /* (frames parsed by aa_stream_parse / aa_stream_decode) */
 
 /* Quantizer::Quantizer( QuantIndices ) (quantization.cc:83-93): out = {y_dc, y_ac, y2_dc, y2_ac, uv_dc, uv_ac} for the base index
  * y_ac_qi and the header's deltas {y_dc, y2_dc, y2_ac, uv_dc, uv_ac} (NULL: all zero) -- aa_frame_header::quant[0] of a new frame. */

@@ -846,6 +846,29 @@ public:
     return job.frame_index;
   }
 
+  // Frame::serialize (serializer.cc:801-829) for ONE frame this decoder holds as records -- parsed, or appended by rebase /
+  // reencode_as_interframe / aa_stream_append_records (aa_serialize_batch with one job; many decoders at once: the C call): the DCT
+  // partitions are written on the GPU, header and first partition on the host.  `ext`: the rest of the header (aa_parser_last_header_ext of
+  // a parse is a complete one); sub_modes: the SPLITMV sub-block modes of the frame the records came from (aa_parser_last_sub_modes), or
+  // none; advance_state: this decoder's DecoderState follows the written frame, as Encoder::write_frame makes the encoder's
+  // (with probs_before == nullptr only: the frame is coded against the decoder's current tables).  `capacity`: room for the frame, by
+  // default 4 KiB + 768 bytes per macroblock (a frame that needs more is refused with the size in the message).
+  std::vector<uint8_t> serialize( const int frame_index, const aa_frame_header & header, aa_frame_header_ext & ext, const std::vector<uint8_t> & sub_modes = {},
+                                  const bool advance_state = true, const uint8_t * probs_before = nullptr, size_t capacity = 0 )
+  {
+    if ( !capacity ) capacity = 4096 + size_t( header.mb_width ) * header.mb_height * 768;
+    std::vector<uint8_t> out( capacity );
+    aa_serialize_job job;
+    std::memset( &job, 0, sizeof job );
+    job.stream = owner_->stream; job.frame_index = frame_index; job.hdr = &header; job.ext = &ext;
+    job.advance_state = advance_state; job.probs_before = probs_before;
+    job.sub_modes = sub_modes.empty() ? nullptr : sub_modes.data(); job.num_sub_modes = sub_modes.size();
+    job.out = out.data(); job.capacity = out.size();
+    check( aa_serialize_batch( owner_->ctx->get(), &job, 1 ) );
+    out.resize( job.size );
+    return out;
+  }
+
   static std::vector<std::pair<bool, RasterHandle>> get_frame_outputs( const std::vector<Decoder *> & decoders, const std::vector<Chunk> & frames )
   {
     if ( decoders.size() != frames.size() || decoders.empty() ) throw std::invalid_argument( "get_frame_outputs: one frame per decoder" );
