@@ -125,6 +125,11 @@ class RebaseJob(C.Structure):
                 ("num_coeff_blocks", C.c_uint32), ("frame_index", C.c_int)]
 
 
+class RebaseDeviceJob(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("hdr", C.POINTER(FrameHeader)), ("mbs", C.c_void_p), ("target", QualityRef),
+                ("num_coeff_blocks", C.c_uint32), ("num_intra_mbs", C.c_uint32), ("frame_index", C.c_int)]
+
+
 class ReencodeJob(C.Structure):
     _fields_ = [("stream", C.c_void_p), ("hdr", C.POINTER(FrameHeader)), ("target", QualityRef), ("quality", C.c_int), ("append", C.c_int),
                 ("mbs_out", C.c_void_p), ("coeffs_out", C.c_void_p), ("coeff_capacity_blocks", C.c_size_t),
@@ -187,6 +192,7 @@ SYMBOLS = [
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     ("aa_quality_batch_async", C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.POINTER(QualityRef), C.c_int, _P, _P, _P]),
     ("aa_rebase_batch", C.c_int, [_P, C.POINTER(RebaseJob), C.c_int]),
+    ("aa_rebase_device_batch", C.c_int, [_P, C.POINTER(RebaseDeviceJob), C.c_int]),
     ("aa_rebase_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_reencode_batch", C.c_int, [_P, C.POINTER(ReencodeJob), C.c_int]),
     ("aa_reencode_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),

@@ -79,6 +79,20 @@ struct aa_rebase_dev_job {
   uint32_t pad;
 };
 
+// One (stream, new frame) of a rebase whose records stay in HBM (aa_rebase_device_batch), beside its aa_rebase_dev_job: where
+// k_rebase_compact puts the frame -- the frame's own pool piece, laid out as a host-appended frame lies in its chunk -- and what the host
+// knows of it beforehand: the job record (rasters unbound, pointers into the piece) and the intra-row words, both copied by the kernel.
+struct alignas( 16 ) aa_rebase_compact_job {
+  aa_dev_frame frame;                  // the template of *out_frame
+  aa_dev_frame * out_frame;            // the piece's start
+  aa_mb_info * out_mbs;                // mbw * mbh records
+  int16_t * out_coeffs;                // num_coeff_blocks dense blocks
+  unsigned long long * out_rows;       // rows_words words
+  const unsigned long long * rows;     // ... as the host made them, in the slice's piece
+  uint32_t rows_words;
+  uint32_t num_coeff_blocks;           // the frame's blocks as the host summed them: nothing is stored at or beyond this block
+};
+
 // One (stream, new frame) of a re-encode (aa_reencode_batch): the rebase's job -- references, target, reconstruction, dense coefficient
 // slots, masks, quantiser; mbs unused, has_intra 1 -- and what the decision adds: the job's rate model, the records it writes, and a
 // side record per macroblock for the census and the B_PRED trial of its neighbours.
@@ -202,6 +216,11 @@ int launch_quality( const aa_quality_job * jobs, int n_planes, uint32_t max_bloc
 // rebase_kernels.hip: jobs[i] (n of them; max_mbs: the largest job's macroblocks) -> dense coefficients, masks and the unfiltered
 // reconstruction: k_rebase_inter over every inter macroblock, then (any_intra) k_rebase_intra, one wave per job
 int launch_rebase( const aa_rebase_dev_job * jobs, int n, uint32_t max_mbs, bool any_intra, void * stream );
+// rebase_compact_kernels.hip, behind launch_rebase on the same stream: k_rebase_count leaves the stored blocks of run r (256 macroblocks)
+// of job i in partials[i * stride + r] (stride >= the largest job's runs); k_rebase_compact, given the frames' pieces (outs[i]), writes
+// records, dense blocks in parse order, job record and intra-row words there
+int launch_rebase_count( const aa_rebase_dev_job * jobs, int n, uint32_t max_mbs, uint32_t * partials, uint32_t stride, void * stream );
+int launch_rebase_compact( const aa_rebase_dev_job * jobs, const aa_rebase_compact_job * outs, int n, uint32_t max_mbs, const uint32_t * partials, uint32_t stride, void * stream );
 // reencode_kernels.hip: jobs[i] (n of them) -> records, dense coefficients, masks and the unfiltered reconstruction: k_reencode_inter, one
 // workgroup per job; slots: macroblocks of an anti-diagonal a round takes (1..16)
 int launch_reencode( const aa_reencode_dev_job * jobs, int n, int slots, void * stream );

@@ -42,6 +42,7 @@
 #include "coeff_pack.hh"
 #include "hash_chain.hh"
 #include "reencode_search.hh"
+#include "rebase_compact.hh"
 #include "serializer.hh"
 
 // ONE translation unit, this file and the fourteen it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):

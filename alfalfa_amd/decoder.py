@@ -422,19 +422,39 @@ class Context:
                 setattr(hdr, name, header[name])
         return hdr
 
-    def rebase(self, decoders, headers, mbs, targets):
+    def rebase(self, decoders, headers, mbs, targets, records=True):
         """The rebase (aa_rebase_batch; Encoder::update_residues, reencode.cc:236-303), one new frame per decoder: headers[i] (a dict
         as Parser.parse / frame_header return it: quant[0] are the factors divided by, key_frame 0) and mbs[i] (the prediction frame's
         records: modes, references and vectors are kept) with residues recomputed so that the frame decodes to targets[i] from
         decoders[i]'s current references.  targets[i]: (y, u, v) uint8 device tensors of the padded plane shapes, edge-extended by the
         caller (rows may be padded), or one contiguous uint8 device tensor holding the three padded planes back to back.
         -> per job (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]) in the shapes Decoder.read_records returns; the frame is
-        appended to its decoder and is decoded like any other (Context.decode_batch).  Synchronous."""
+        appended to its decoder and is decoded like any other (Context.decode_batch).  Synchronous.
+        records=False (aa_rebase_device_batch): the new frame's records are compacted on the device and stay there -- nothing but a few
+        count words comes down -- and the result per job is (frame_index, num_coeff_blocks); Decoder.read_records gives the records
+        to whoever wants them on the host, Context.serialize_frames and Context.decode_batch take the frame where it lies."""
         import torch
         n = len(decoders)
         if n == 0 or len(headers) != n or len(mbs) != n or len(targets) != n:
             raise ValueError("rebase: need as many headers, records and targets as decoders, and at least one")
         device = torch.device("cuda", self.device)
+        if not records:
+            jobs = (capi.RebaseDeviceJob * n)()
+            keep = []
+            for i, (d, header, mb, t) in enumerate(zip(decoders, headers, mbs, targets)):
+                t = self._target_planes("rebase", i, d, t)
+                hdr = self._header_struct(header)
+                rec = np.ascontiguousarray(mb, dtype=MB_INFO_DTYPE).reshape(-1)
+                if len(rec) != hdr.mb_width * hdr.mb_height:
+                    raise ValueError("rebase: mbs[%d] holds %d records, the header says %d" % (i, len(rec), hdr.mb_width * hdr.mb_height))
+                j = jobs[i]
+                j.stream, j.hdr, j.mbs = d.h, C.pointer(hdr), rec.ctypes.data_as(C.c_void_p)
+                j.target.y, j.target.u, j.target.v = t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr()
+                j.target.y_stride, j.target.uv_stride = t[0].stride(0), t[1].stride(0)
+                keep.append((hdr, rec, t))
+            torch.cuda.current_stream(device).synchronize()
+            capi.check(self.L.aa_rebase_device_batch(self.h, jobs, n))
+            return [(jobs[i].frame_index, jobs[i].num_coeff_blocks) for i in range(n)]
         jobs = (capi.RebaseJob * n)()
         keep, outs = [], []
         for i, (d, header, mb, t) in enumerate(zip(decoders, headers, mbs, targets)):
@@ -458,7 +478,8 @@ class Context:
         return [(jobs[i].frame_index, mb_out.reshape(mbh, mbw), cf[:jobs[i].num_coeff_blocks].copy()) for i, (mb_out, cf, mbw, mbh) in enumerate(outs)]
 
     def rebase_timing(self):
-        """The last rebase of this context (aa_rebase_last_timing), ms: call, upload + kernels, download, host records, append."""
+        """The last rebase of this context (aa_rebase_last_timing), ms: call, upload + kernels, download, host records, append (for a
+        rebase with records=False: the download is the count words, the host records are 0, the append is bookkeeping)."""
         out = (C.c_double * 5)()
         capi.check(self.L.aa_rebase_last_timing(self.h, out))
         return dict(zip(("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms"), out))
@@ -687,9 +708,10 @@ class Decoder:
         capi.check(self.L.aa_stream_append_records(self.h, C.byref(hdr), mbs.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p), C.byref(fi)))
         return fi.value
 
-    def rebase(self, header, mb, target):
-        """One new frame of this decoder by rebase (Context.rebase) -> (frame_index, mb [mbh, mbw], coeff_blocks [n, 16])."""
-        return self.ctx.rebase([self], [header], [mb], [target])[0]
+    def rebase(self, header, mb, target, records=True):
+        """One new frame of this decoder by rebase (Context.rebase) -> (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]), or with
+        records=False (frame_index, num_coeff_blocks) and the records left on the device."""
+        return self.ctx.rebase([self], [header], [mb], [target], records=records)[0]
 
     def reencode_as_inter(self, header, target, quality="best", append=True):
         """One new frame of this decoder by re-encode (Context.reencode_as_inter) -> (frame_index, mb [mbh, mbw], coeff_blocks [n, 16])."""

@@ -534,6 +534,21 @@ aa_status aa_rebase_batch( aa_ctx * ctx, aa_rebase_job * jobs, int n );
  * and the two kernels, [2] coefficients and masks down (HIP events on the compute stream, summed over the call's slices); [3] the
  * records built on the host, [4] the frames appended (wall clock).  For tools/rebase_probe.py. */
 aa_status aa_rebase_last_timing( aa_ctx * ctx, double out[5] );
+/* The same rebase with the new frame's records KEPT ON THE DEVICE: the two kernels of aa_rebase_batch, then k_rebase_count and
+ * k_rebase_compact, which turn the masks and dense slots into the frame's records -- flags, nz_mask, coeff_index, the stored blocks in
+ * parse order: byte for byte what aa_rebase_batch returns -- inside a piece of HBM that is the frame's from then on.  Nothing of the
+ * records crosses the bus: per frame a few count words come down (the blocks stored per run of 256 macroblocks).  The frame is
+ * appended to its stream and taken by aa_decode_batch, aa_serialize_batch, aa_stream_read_records, aa_stream_frame_header, release and
+ * rewind like any other; a caller who wants the records on the host reads them back (aa_stream_read_records).  Synchronous.
+ * num_coeff_blocks, num_intra_mbs (out): what the appended frame's header says.  Arguments, refusals and slicing as aa_rebase_batch's
+ * (the messages begin "aa_rebase_device_batch:"; nothing is appended to any stream of a refused or failed call).
+ * aa_rebase_last_timing reports this call too: [1] both uploads and the four kernels, [2] the count words down, [3] 0, [4] the
+ * bookkeeping of the append.  (Still AA_ABI_VERSION 4: an addition, as the serialisation was.) */
+typedef struct aa_rebase_device_job {
+  aa_stream * stream; const aa_frame_header * hdr; const aa_mb_info * mbs; aa_quality_ref target;   /* as aa_rebase_job's */
+  uint32_t num_coeff_blocks, num_intra_mbs; int frame_index;                                        /* out */
+} aa_rebase_device_job;
+aa_status aa_rebase_device_batch( aa_ctx * ctx, aa_rebase_device_job * jobs, int n );
 
 /* The RE-ENCODE (Encoder::reencode_as_interframe, reencode.cc:38-129, the first thing xc-enc -r does to a chunk): the chunk's key frame
  * is encoded again as an inter frame predicted from the references the stream holds NOW -- the frame that joins two chunks.  Per
@@ -568,8 +583,9 @@ aa_status aa_reencode_last_timing( aa_ctx * ctx, double out[5] );
  * context creation): with a small cap the several-rounds-per-diagonal path runs on a small frame (tests). */
 aa_status aa_ctx_set_reencode_slots( aa_ctx * ctx, int slots );
 
-/* SERIALISATION (Frame::serialize, serializer.cc:388-829): frame `frame_index` of `stream`, held as records -- parsed from bytes, or appended
- * by aa_rebase_batch / aa_reencode_batch / aa_stream_append_records -- becomes a VP8 frame in `out`.  The DCT partitions are written on the
+/* SERIALISATION (Frame::serialize, serializer.cc:388-829): frame `frame_index` of `stream`, held as records -- parsed from bytes, appended
+ * by aa_rebase_batch / aa_reencode_batch / aa_stream_append_records, or device-resident (aa_rebase_device_batch: its 80-byte macroblock
+ * records are copied back for the first partition, its blocks never leave HBM) -- becomes a VP8 frame in `out`.  The DCT partitions are written on the
  * device from the records where they lie, dense or packed (k_serialize_tokens: a lane per job and partition, partition p takes the
  * macroblock rows r % num_dct_partitions == p); meanwhile host workers, one job each, write the frame header and the macroblock headers of
  * the first partition from the macroblock records (the same boolean encoder, bool_writer.hh) and then put the frame together: tag, key-frame

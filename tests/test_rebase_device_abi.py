@@ -1,0 +1,40 @@
+"""The device-resident rebase's entry point without a GPU: aa_rebase_device_batch is exported and bound, refuses null arguments, the
+ABI version stays what it was (a symbol and a struct were added, nothing existing changed), and the bindings' aa_rebase_device_job has
+the size and the field offsets a C compiler gives the header's."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from alfalfa_amd import capi
+from conftest import ROOT
+
+HEADER_DIR = os.path.join(ROOT, "include")
+
+
+def test_the_entry_point_is_exported_and_the_version_is_unchanged():
+    L = capi.lib()
+    assert hasattr(L, "aa_rebase_device_batch") and "aa_rebase_device_batch" in {n for n, _, _ in capi.SYMBOLS}
+    assert "aa_rebase_device_batch(" in open(os.path.join(HEADER_DIR, "alfalfa_amd.h")).read()
+    assert L.aa_abi_version() == 4
+
+
+def test_null_arguments_are_refused_without_a_device():
+    L = capi.lib()
+    assert L.aa_rebase_device_batch(None, None, 0) == -7
+    assert b"aa_rebase_device_batch" in L.aa_last_error()
+
+
+@pytest.mark.skipif(not shutil.which("gcc"), reason="gcc is not installed")
+def test_the_job_struct_is_the_header_s(tmp_path):
+    fields = [n for n, _ in capi.RebaseDeviceJob._fields_]
+    src, exe = str(tmp_path / "size.c"), str(tmp_path / "size")
+    with open(src, "w") as f:
+        f.write('#include <stdio.h>\n#include <stddef.h>\n#include "alfalfa_amd.h"\nint main( void ) { printf( "%zu'
+                + " %zu" * len(fields) + '\\n", sizeof( aa_rebase_device_job )' + "".join(", offsetof( aa_rebase_device_job, %s )" % n for n in fields) + " ); return 0; }\n")
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", HEADER_DIR, src, "-o", exe], check=True)
+    got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    assert got == [C.sizeof(capi.RebaseDeviceJob)] + [getattr(capi.RebaseDeviceJob, n).offset for n in fields]
+    assert got[0] == 80

@@ -7,7 +7,11 @@ appended (HIP events on the compute stream).  Every repetition rebases onto the 
 refresh LAST), so the work is the same each time.  Before anything is printed a sample of the decoded new frames is compared with its
 target (mean absolute luma error; a rebased frame comes out within the quantiser's error of it).
 
-    python tools/rebase_probe.py [--reps 3] [--warmup 1] [--streams 120] [--copies 4] [--out results.json]
+    python tools/rebase_probe.py [--reps 3] [--warmup 1] [--streams 120] [--copies 4] [--device] [--out results.json]
+
+--device: afterwards, in the same process, the same frames on twin decoders through aa_rebase_device_batch (Context.rebase( records=False ):
+the records compacted on the device and kept there); its figures go under "device" in the result, the download leg being the count
+words alone, the host-records leg 0 and the append leg bookkeeping.
 
 Kernel times (k_rebase_inter, k_rebase_intra, and k_recon_inter4 on the same frames -- the yardstick: the inter kernel does that
 kernel's loads plus one read of the target and an 800-byte store per macroblock): a run of its own under
@@ -37,6 +41,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--sample", type=int, default=4, help="new frames compared with their targets")
     ap.add_argument("--out", help="also write the results as JSON to this file")
+    ap.add_argument("--device", action="store_true", help="then the same frames on twin decoders through aa_rebase_device_batch (records kept in HBM)")
     args = ap.parse_args()
     import torch
     import workload
@@ -67,53 +72,63 @@ def main():
         targets.append(tuple(planes))
         del d
     torch.cuda.synchronize()
-    decs = []
-    for c in range(args.copies):
-        for i in range(len(paths)):
-            d = aa.Decoder(ctx, *size)
-            d.get_frame_output(keys[i])
-            decs.append(d)
+    decs, twins = [], []
+    for group in [decs] + ([twins] if args.device else []):
+        for c in range(args.copies):
+            for i in range(len(paths)):
+                d = aa.Decoder(ctx, *size)
+                d.get_frame_output(keys[i])
+                group.append(d)
     ctx.sync()
     n = len(decs)
     b_hdr, b_mb, b_t = headers * args.copies, records * args.copies, targets * args.copies
     nmb = sum(m.size for m in b_mb)
     intra = sum(int((m["ref_frame"] == 0).sum()) for m in b_mb)
     compute = torch.cuda.ExternalStream(ctx.compute_stream(), device=torch.device("cuda", ctx.device))
-    runs = []
-    for rep in range(args.warmup + args.reps):
-        t0 = time.perf_counter()
-        results = ctx.rebase(decs, b_hdr, b_mb, b_t)
-        wall_py = (time.perf_counter() - t0) * 1e3
-        timing = ctx.rebase_timing()
-        fis = [r[0] for r in results]
-        blocks = sum(len(r[2]) for r in results)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record(compute)
-        ctx.decode_batch(decs, fis)
-        ev[1].record(compute)
-        ev[1].synchronize()
-        timing["decode_batch_ms"] = ev[0].elapsed_time(ev[1])
-        timing["python_call_ms"] = wall_py
-        timing["coeff_blocks"] = blocks
-        if rep == args.warmup + args.reps - 1:
-            for k in np.linspace(0, n - 1, args.sample).astype(int):
-                y = decs[k].raster(fis[k])[0].astype(np.int32)
-                err = np.abs(y - b_t[k][0].cpu().numpy().astype(np.int32)).mean()
-                timing.setdefault("sample_mean_abs_luma_error", []).append(round(float(err), 3))
-                if err > 8:
-                    print("rebase_probe: WARNING: decoder %d's new frame is %.2f grey levels from its target on average" % (k, err), file=sys.stderr)
-        for d, fi in zip(decs, fis):
-            d.release_before(fi)
-        del results
-        if rep >= args.warmup:
-            runs.append(timing)
-    mean = {k: float(np.mean([r[k] for r in runs])) for k in ("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms", "decode_batch_ms", "python_call_ms")}
-    out = {"config": args.config, "frames": n, "macroblocks": nmb, "intra_macroblocks": intra, "reps": args.reps, "runs": runs, "mean": mean,
-           "macroblocks_per_s_call": nmb / mean["call_ms"] * 1e3, "macroblocks_per_s_kernels": nmb / mean["kernels_ms"] * 1e3,
-           "share_download": mean["download_ms"] / mean["call_ms"], "share_host_records": mean["records_ms"] / mean["call_ms"],
-           "share_append": mean["append_ms"] / mean["call_ms"]}
-    print("rebase of %d frames (%d macroblocks, %d intra): call %.1f ms = up + kernels %.1f, download %.1f, host records %.1f, append %.1f; %.1f M macroblocks/s; decode_batch of the same frames %.1f ms"
-          % (n, nmb, intra, mean["call_ms"], mean["kernels_ms"], mean["download_ms"], mean["records_ms"], mean["append_ms"], out["macroblocks_per_s_call"] / 1e6, mean["decode_batch_ms"]), flush=True)
+
+    def measure(decs, on_device):
+        runs = []
+        for rep in range(args.warmup + args.reps):
+            t0 = time.perf_counter()
+            results = ctx.rebase(decs, b_hdr, b_mb, b_t, records=not on_device)
+            wall_py = (time.perf_counter() - t0) * 1e3
+            timing = ctx.rebase_timing()
+            fis = [r[0] for r in results]
+            blocks = sum(r[1] if on_device else len(r[2]) for r in results)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record(compute)
+            ctx.decode_batch(decs, fis)
+            ev[1].record(compute)
+            ev[1].synchronize()
+            timing["decode_batch_ms"] = ev[0].elapsed_time(ev[1])
+            timing["python_call_ms"] = wall_py
+            timing["coeff_blocks"] = blocks
+            if rep == args.warmup + args.reps - 1:
+                for k in np.linspace(0, n - 1, args.sample).astype(int):
+                    y = decs[k].raster(fis[k])[0].astype(np.int32)
+                    err = np.abs(y - b_t[k][0].cpu().numpy().astype(np.int32)).mean()
+                    timing.setdefault("sample_mean_abs_luma_error", []).append(round(float(err), 3))
+                    if err > 8:
+                        print("rebase_probe: WARNING: decoder %d's new frame is %.2f grey levels from its target on average" % (k, err), file=sys.stderr)
+            for d, fi in zip(decs, fis):
+                d.release_before(fi)
+            del results
+            if rep >= args.warmup:
+                runs.append(timing)
+        mean = {k: float(np.mean([r[k] for r in runs])) for k in ("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms", "decode_batch_ms", "python_call_ms")}
+        out = {"config": args.config, "frames": n, "macroblocks": nmb, "intra_macroblocks": intra, "reps": args.reps, "runs": runs, "mean": mean,
+               "macroblocks_per_s_call": nmb / mean["call_ms"] * 1e3, "macroblocks_per_s_kernels": nmb / mean["kernels_ms"] * 1e3,
+               "share_download": mean["download_ms"] / mean["call_ms"], "share_host_records": mean["records_ms"] / mean["call_ms"],
+               "share_append": mean["append_ms"] / mean["call_ms"]}
+        print("rebase%s of %d frames (%d macroblocks, %d intra): call %.1f ms = up + kernels %.1f, download %.1f, host records %.1f, append %.1f; %.1f M macroblocks/s; decode_batch of the same frames %.1f ms"
+              % (", records kept on the device," if on_device else "", n, nmb, intra, mean["call_ms"], mean["kernels_ms"], mean["download_ms"], mean["records_ms"], mean["append_ms"],
+                 out["macroblocks_per_s_call"] / 1e6, mean["decode_batch_ms"]), flush=True)
+        return out
+
+    out = measure(decs, False)
+    if args.device:
+        out["device"] = measure(twins, True)
+        out["device"]["coeff_blocks_equal_host_path"] = out["device"]["runs"][-1]["coeff_blocks"] == out["runs"][-1]["coeff_blocks"]
     print(json.dumps(out))
     if args.out:
         with open(args.out, "w") as f:

@@ -10,7 +10,10 @@ call, on as many worker threads as the process has cores (aa_host_cpus; argument
 and the bytes compared with the GPU's.  Before anything is printed a sample of the written frames is parsed back and compared with the records
 the rebase returned.
 
-    python tools/serialize_probe.py [--reps 3] [--warmup 1] [--streams 120] [--copies 4] [--out results.json]
+    python tools/serialize_probe.py [--reps 3] [--warmup 1] [--streams 120] [--copies 4] [--device] [--out results.json]
+
+--device: the rebase leg is aa_rebase_device_batch (Context.rebase( records=False )): the frames' records stay in HBM, the serialiser
+copies back the 80-byte macroblock records alone, and the records the host's chains are given are read back outside the timed legs.
 
 profiles/serialize_batch.md holds what was measured."""
 import argparse
@@ -41,6 +44,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--sample", type=int, default=4, help="written frames parsed back and compared with the rebase's records")
     ap.add_argument("--out", help="also write the results as JSON to this file")
+    ap.add_argument("--device", action="store_true", help="the rebase leg through aa_rebase_device_batch: the serialiser reads records that never left HBM")
     args = ap.parse_args()
     import torch
     import workload
@@ -90,13 +94,15 @@ def main():
     capacity = 4096 + (nmb // n) * 400          # bytes per frame: half the raw size of a frame's coefficients and more than any of these takes
     runs = []
     for rep in range(args.warmup + args.reps):
-        results = ctx.rebase(decs, b_hdr, b_mb, b_t)
+        results = ctx.rebase(decs, b_hdr, b_mb, b_t, records=not args.device)
         rebase = ctx.rebase_timing()
         fis = [r[0] for r in results]
         t0 = time.perf_counter()
         frames = ctx.serialize_frames(decs, fis, b_hdr, b_ext, probs_before=b_before, sub_modes=b_subs, capacity=capacity)
         wall_py = (time.perf_counter() - t0) * 1e3
         timing = ctx.serialize_timing()
+        if args.device:                     # (the host's chains below and the parse-back want the records: read back here, outside every timed leg)
+            results = [(fi,) + d.read_records(fi)[1:] for d, fi in zip(decs, fis)]
         timing = {"serialize_" + key: v for key, v in timing.items()}
         timing.update({"rebase_" + key: v for key, v in rebase.items()})
         timing["serialize_python_call_ms"] = wall_py
