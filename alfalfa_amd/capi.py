@@ -136,6 +136,11 @@ class ReencodeJob(C.Structure):
                 ("num_coeff_blocks", C.c_uint32), ("frame_index", C.c_int)]
 
 
+class ReencodeDeviceJob(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("hdr", C.POINTER(FrameHeader)), ("target", QualityRef), ("quality", C.c_int),
+                ("num_coeff_blocks", C.c_uint32), ("num_intra_mbs", C.c_uint32), ("frame_index", C.c_int)]
+
+
 class AlfalfaError(RuntimeError):
     """Mirrors the reference's exception types (exception.hh:76-98) by name in `.kind`."""
 
@@ -195,6 +200,7 @@ SYMBOLS = [
     ("aa_rebase_device_batch", C.c_int, [_P, C.POINTER(RebaseDeviceJob), C.c_int]),
     ("aa_rebase_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_reencode_batch", C.c_int, [_P, C.POINTER(ReencodeJob), C.c_int]),
+    ("aa_reencode_device_batch", C.c_int, [_P, C.POINTER(ReencodeDeviceJob), C.c_int]),
     ("aa_reencode_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_ctx_set_reencode_slots", C.c_int, [_P, C.c_int]),
     ("aa_parser_last_header_ext", C.c_int, [_P, C.POINTER(FrameHeaderExt)]), ("aa_stream_last_header_ext", C.c_int, [_P, C.POINTER(FrameHeaderExt)]),

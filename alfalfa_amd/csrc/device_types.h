@@ -101,6 +101,7 @@ struct aa_reencode_dev_job {
   const void * costs;          // aa::ReencCosts (reencode_search.hh)
   aa_mb_info * mbs_out;        // mbw * mbh records: y_mode, uv_mode, ref_frame, nz_mask and u are the kernel's, the rest is zero
   uint32_t * nb;               // [mbw * mbh][4]: aa::ReencNeighbour
+  unsigned long long * intra_rows;   // aa_reencode_device_batch: where k_reencode_count leaves the frame's intra-row words (else null, unused)
 };
 
 // One (stream, frame) of a serialisation (aa_serialize_batch): the frame's records as reconstruction reads them, the tables its tokens are
@@ -224,6 +225,12 @@ int launch_rebase_compact( const aa_rebase_dev_job * jobs, const aa_rebase_compa
 // reencode_kernels.hip: jobs[i] (n of them) -> records, dense coefficients, masks and the unfiltered reconstruction: k_reencode_inter, one
 // workgroup per job; slots: macroblocks of an anti-diagonal a round takes (1..16)
 int launch_reencode( const aa_reencode_dev_job * jobs, int n, int slots, void * stream );
+// reencode_compact_kernels.hip, behind launch_reencode on the same stream: the pair of launch_rebase_count / launch_rebase_compact over the
+// records the decision wrote.  k_reencode_count also leaves every frame's intra-row words in jobs[i].intra_rows; k_reencode_compact copies
+// them from there (outs[i].rows) and sets lf_level by lf[i] (aa::HeaderParams, n of them)
+int launch_reencode_count( const aa_reencode_dev_job * jobs, int n, uint32_t max_mbs, uint32_t * partials, uint32_t stride, void * stream );
+int launch_reencode_compact( const aa_reencode_dev_job * jobs, const aa_rebase_compact_job * outs, const void * lf, int n, uint32_t max_mbs, const uint32_t * partials, uint32_t stride,
+                             void * stream );
 // serialize_kernels.hip: k_serialize_tokens, a lane per (job, DCT partition): lanes[i] = job << 3 | partition, n_lanes of them,
 // lanes_per_wave (1..64) to a wave
 int launch_serialize_tokens( const aa_serialize_dev_job * jobs, const uint32_t * lanes, int n_lanes, int lanes_per_wave, void * stream );

@@ -17,18 +17,19 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 
-#include "device_types.h"
-#include "rebase_compact.hh"
+#include "compact_device.hh"      // the statements shared with the re-encode's pair (reencode_compact_kernels.hip)
 
 namespace aa {
 
 namespace {
 
-constexpr int kCompactThreads = static_cast<int>( compact::kCompactMbs );
-constexpr int kCompactWaves = kCompactThreads / 64;
-static_assert( sizeof( aa_mb_info ) == 80 && sizeof( aa_dev_frame ) % 16 == 0 && sizeof( aa_dev_frame ) / 16 <= kCompactThreads, "records and job record move as 16-byte units" );
+using compact::kCompactThreads;
+using compact::kCompactWaves;
 
-union RecordUnits { aa_mb_info mb; uint4 q[5]; };
+// a rebased frame's output record: the input's with the residue fields set
+struct RebaseRecord {
+  __device__ __forceinline__ aa_mb_info operator()( const aa_mb_info & m, const uint32_t raw, const uint32_t index ) const { return compact::output_record( m, raw, index ); }
+};
 
 } // namespace
 
@@ -40,17 +41,8 @@ __global__ __launch_bounds__( kCompactThreads ) void k_rebase_count( const aa_re
   const uint32_t first = blockIdx.x * compact::kCompactMbs;
   if ( first >= total ) return;                             // (whole workgroup: jobs of one call may differ in size)
   const uint32_t mi = first + threadIdx.x;
-  uint32_t n = mi < total ? compact::popc( compact::stored_mask( J.masks[mi], J.mbs[mi].y_mode ) ) : 0u;
-#pragma unroll
-  for ( int off = 32; off; off >>= 1 ) n += __shfl_down( n, off );
-  if ( ( threadIdx.x & 63 ) == 0 ) wave_sum[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if ( threadIdx.x == 0 ) {
-    uint32_t sum = 0;
-#pragma unroll
-    for ( int w = 0; w < kCompactWaves; w++ ) sum += wave_sum[w];
-    partials[static_cast<size_t>( blockIdx.y ) * stride + blockIdx.x] = sum;
-  }
+  const uint32_t n = mi < total ? compact::popc( compact::stored_mask( J.masks[mi], J.mbs[mi].y_mode ) ) : 0u;
+  compact::run_sum( n, wave_sum, partials + static_cast<size_t>( blockIdx.y ) * stride + blockIdx.x );
 }
 
 __global__ __launch_bounds__( kCompactThreads ) void k_rebase_compact( const aa_rebase_dev_job * jobs, const aa_rebase_compact_job * outs, const uint32_t * partials, uint32_t stride )
@@ -58,69 +50,9 @@ __global__ __launch_bounds__( kCompactThreads ) void k_rebase_compact( const aa_
   __shared__ uint32_t run_mask[kCompactThreads], run_index[kCompactThreads];
   __shared__ uint32_t wave_sum[kCompactWaves];
   const aa_rebase_dev_job & J = jobs[blockIdx.y];
-  const aa_rebase_compact_job & O = outs[blockIdx.y];
   const uint32_t total = static_cast<uint32_t>( J.mbw ) * J.mbh;
-  const uint32_t first = blockIdx.x * compact::kCompactMbs;
-  if ( first >= total ) return;
-  const uint32_t in_run = total - first < compact::kCompactMbs ? total - first : compact::kCompactMbs;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t base = compact::run_base( partials + static_cast<size_t>( blockIdx.y ) * stride, blockIdx.x );
-
-  // ---- this thread's macroblock: record in, stored mask, its place in the frame by a scan of the run ----
-  const uint32_t mi = first + tid;
-  const bool have = mi < total;
-  RecordUnits R;
-  uint32_t raw = 0;
-  if ( have ) {
-    const uint4 * src = reinterpret_cast<const uint4 *>( J.mbs + mi );
-#pragma unroll
-    for ( int k = 0; k < 5; k++ ) R.q[k] = src[k];
-    raw = J.masks[mi];
-  } else {
-#pragma unroll
-    for ( int k = 0; k < 5; k++ ) R.q[k] = make_uint4( 0, 0, 0, 0 );
-  }
-  const uint32_t mask = compact::stored_mask( raw, R.mb.y_mode );
-  const uint32_t n = compact::popc( mask );
-  uint32_t incl = n;
-#pragma unroll
-  for ( int off = 1; off < 64; off <<= 1 ) {
-    const uint32_t v = __shfl_up( incl, off );
-    if ( lane >= static_cast<uint32_t>( off ) ) incl += v;
-  }
-  if ( lane == 63 ) wave_sum[wave] = incl;
-  __syncthreads();
-  uint32_t before = base;
-#pragma unroll
-  for ( int w = 0; w < kCompactWaves; w++ ) if ( static_cast<uint32_t>( w ) < wave ) before += wave_sum[w];
-  const uint32_t index = before + incl - n;
-  run_mask[tid] = mask; run_index[tid] = index;
-  if ( have ) {
-    R.mb = compact::output_record( R.mb, raw, index );
-    uint4 * dst = reinterpret_cast<uint4 *>( O.out_mbs + mi );
-#pragma unroll
-    for ( int k = 0; k < 5; k++ ) dst[k] = R.q[k];
-  }
-  // ---- run 0: the frame's job record and intra-row words ----
-  if ( blockIdx.x == 0 ) {
-    if ( tid < sizeof( aa_dev_frame ) / 16 ) reinterpret_cast<uint4 *>( O.out_frame )[tid] = reinterpret_cast<const uint4 *>( &O.frame )[tid];
-    for ( uint32_t w = tid; w < O.rows_words; w += kCompactThreads ) O.out_rows[w] = O.rows[w];
-  }
-  __syncthreads();
-
-  // ---- the run's slots, 16 bytes a thread and trip ----
-  const uint8_t * dense = reinterpret_cast<const uint8_t *>( J.coeffs ) + static_cast<size_t>( first ) * AA_REBASE_MB_BYTES;
-  uint8_t * blocks = reinterpret_cast<uint8_t *>( O.out_coeffs );
-  const uint32_t units = in_run * compact::kUnitsPerMb;
-  for ( uint32_t u = tid; u < units; u += kCompactThreads ) {
-    const compact::Unit x = compact::unit_of( u );
-    const uint32_t m = run_mask[x.mb];
-    if ( !compact::unit_stored( x, m ) ) continue;
-    const uint32_t block = compact::unit_block( x, m, run_index[x.mb] );
-    if ( block >= O.num_coeff_blocks ) continue;            // (cannot happen while the host's sum is this kernel's: nothing is ever stored outside the piece)
-    const uint4 v = *reinterpret_cast<const uint4 *>( dense + compact::unit_source( x ) );
-    *reinterpret_cast<uint4 *>( blocks + static_cast<size_t>( block ) * 32 + x.half * 16 ) = v;
-  }
+  if ( blockIdx.x * compact::kCompactMbs >= total ) return;
+  compact::compact_run( J.mbs, J.masks, J.coeffs, total, outs[blockIdx.y], partials + static_cast<size_t>( blockIdx.y ) * stride, run_mask, run_index, wave_sum, RebaseRecord() );
 }
 
 int launch_rebase_count( const aa_rebase_dev_job * jobs, int n, uint32_t max_mbs, uint32_t * partials, uint32_t stride, void * stream )

@@ -43,6 +43,7 @@
 #include "hash_chain.hh"
 #include "reencode_search.hh"
 #include "rebase_compact.hh"
+#include "reencode_compact.hh"
 #include "serializer.hh"
 
 // ONE translation unit, this file and the fourteen it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):

@@ -484,13 +484,16 @@ class Context:
         capi.check(self.L.aa_rebase_last_timing(self.h, out))
         return dict(zip(("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms"), out))
 
-    def reencode_as_inter(self, decoders, headers, targets, quality="best", append=True):
+    def reencode_as_inter(self, decoders, headers, targets, quality="best", append=True, records=True):
         """The re-encode (aa_reencode_batch; Encoder::reencode_as_interframe, reencode.cc:38-129), one new frame per decoder: targets[i]
         -- a chunk's first picture -- encoded as an inter frame predicted from decoders[i]'s current last reference, every macroblock's
         mode chosen as the reference's encoder chooses it (quality: "best" or "rt", for all jobs or one per job).  headers[i] and
         targets[i] as for rebase.  -> per job (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]) as rebase returns them; with append
         False nothing is appended and frame_index is -1 (the records go through Decoder.append_records when the frame is final).
-        Synchronous."""
+        Synchronous.
+        records=False (aa_reencode_device_batch): the new frame's records are compacted on the device and stay there, as with
+        rebase( records=False ) -- the result per job is (frame_index, num_coeff_blocks).  Such a frame is always appended: together
+        with append=False this raises ValueError."""
         import torch
         n = len(decoders)
         if n == 0 or len(headers) != n or len(targets) != n:
@@ -498,6 +501,22 @@ class Context:
         qualities = [quality] * n if isinstance(quality, str) else list(quality)
         if len(qualities) != n or any(q not in ("best", "rt") for q in qualities):
             raise ValueError("reencode_as_inter: quality is \"best\" or \"rt\", one for all jobs or one per job")
+        if not records:
+            if not append:
+                raise ValueError("reencode_as_inter: records=False keeps the frame on the device, where it is always appended; append=False needs records=True")
+            jobs = (capi.ReencodeDeviceJob * n)()
+            keep = []
+            for i, (d, header, t) in enumerate(zip(decoders, headers, targets)):
+                t = self._target_planes("reencode_as_inter", i, d, t)
+                hdr = self._header_struct(header)
+                j = jobs[i]
+                j.stream, j.hdr, j.quality = d.h, C.pointer(hdr), (1 if qualities[i] == "rt" else 0)
+                j.target.y, j.target.u, j.target.v = t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr()
+                j.target.y_stride, j.target.uv_stride = t[0].stride(0), t[1].stride(0)
+                keep.append((hdr, t))
+            torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
+            capi.check(self.L.aa_reencode_device_batch(self.h, jobs, n))
+            return [(jobs[i].frame_index, jobs[i].num_coeff_blocks) for i in range(n)]
         jobs = (capi.ReencodeJob * n)()
         keep, outs = [], []
         for i, (d, header, t) in enumerate(zip(decoders, headers, targets)):
@@ -576,7 +595,8 @@ class Context:
         return dict(zip(("call_ms", "kernel_ms", "download_ms", "first_partition_ms", "assemble_ms"), out))
 
     def reencode_timing(self):
-        """The last re-encode of this context (aa_reencode_last_timing), ms: call, upload + kernel, download, host records, append."""
+        """The last re-encode of this context (aa_reencode_last_timing), ms: call, upload + kernel, download, host records, append (for a
+        re-encode with records=False: the download is the count and row words, the host records are 0, the append is bookkeeping)."""
         out = (C.c_double * 5)()
         capi.check(self.L.aa_reencode_last_timing(self.h, out))
         return dict(zip(("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms"), out))
@@ -713,9 +733,10 @@ class Decoder:
         records=False (frame_index, num_coeff_blocks) and the records left on the device."""
         return self.ctx.rebase([self], [header], [mb], [target], records=records)[0]
 
-    def reencode_as_inter(self, header, target, quality="best", append=True):
-        """One new frame of this decoder by re-encode (Context.reencode_as_inter) -> (frame_index, mb [mbh, mbw], coeff_blocks [n, 16])."""
-        return self.ctx.reencode_as_inter([self], [header], [target], quality, append)[0]
+    def reencode_as_inter(self, header, target, quality="best", append=True, records=True):
+        """One new frame of this decoder by re-encode (Context.reencode_as_inter) -> (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]), or
+        with records=False (frame_index, num_coeff_blocks)."""
+        return self.ctx.reencode_as_inter([self], [header], [target], quality, append, records)[0]
 
     def serialize_frame(self, frame_index, header, ext, probs_before=None, advance_state=False, capacity=None, sub_modes=None, optimise=False, details=False):
         """One frame of this decoder, held as records, as VP8 bytes (Context.serialize_frames)."""

@@ -577,14 +577,32 @@ typedef struct aa_reencode_job {
   uint32_t num_coeff_blocks; int frame_index;                                  /* out */
 } aa_reencode_job;
 aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n );
-/* As aa_rebase_last_timing, for the last successful aa_reencode_batch: [1] job table and rate models up and the kernel. */
+/* The same re-encode with the new frame's records KEPT ON THE DEVICE, as aa_rebase_device_batch keeps a rebased frame's: behind the
+ * kernel of aa_reencode_batch, k_reencode_count and k_reencode_compact turn the records, masks and dense slots it left into the frame's
+ * records -- flags, nz_mask, coeff_index, lf_level, the stored blocks in parse order: byte for byte what aa_reencode_batch returns --
+ * inside a piece of HBM that is the frame's from then on.  Nothing of the records crosses the bus: per frame the blocks stored per run
+ * of 256 macroblocks and the intra-row words come down (the modes are decided on the device, so the intra count and the diagonals are
+ * derived from those words).  There is no `append` field: a frame that stays on the device is always appended to its stream, and is
+ * taken by aa_decode_batch, aa_serialize_batch, aa_stream_read_records, aa_stream_frame_header, release and rewind like any other; a
+ * caller who wants the records before the frame is final keeps using aa_reencode_batch with append = 0.  Synchronous.
+ * num_coeff_blocks, num_intra_mbs (out): what the appended frame's header says.  Arguments, refusals and slicing as aa_reencode_batch's,
+ * but for the coefficient capacity, which has no counterpart (the messages begin "aa_reencode_device_batch:"; nothing is appended to
+ * any stream of a refused or failed call).  aa_reencode_last_timing reports this call too: [1] both uploads and the three kernels,
+ * [2] the count words and row words down, [3] 0, [4] the bookkeeping of the append.  (Still AA_ABI_VERSION 4: an addition.) */
+typedef struct aa_reencode_device_job {
+  aa_stream * stream; const aa_frame_header * hdr; aa_quality_ref target; int quality;   /* as aa_reencode_job's */
+  uint32_t num_coeff_blocks, num_intra_mbs; int frame_index;                              /* out */
+} aa_reencode_device_job;
+aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs, int n );
+/* As aa_rebase_last_timing, for the last successful aa_reencode_batch (or aa_reencode_device_batch, see there): [1] job table and rate
+ * models up and the kernel. */
 aa_status aa_reencode_last_timing( aa_ctx * ctx, double out[5] );
 /* How many macroblocks of an anti-diagonal a round of the re-encode kernel takes (1..16, default 16; also ALFALFA_AMD_REENC_SLOTS at
  * context creation): with a small cap the several-rounds-per-diagonal path runs on a small frame (tests). */
 aa_status aa_ctx_set_reencode_slots( aa_ctx * ctx, int slots );
 
 /* SERIALISATION (Frame::serialize, serializer.cc:388-829): frame `frame_index` of `stream`, held as records -- parsed from bytes, appended
- * by aa_rebase_batch / aa_reencode_batch / aa_stream_append_records, or device-resident (aa_rebase_device_batch: its 80-byte macroblock
+ * by aa_rebase_batch / aa_reencode_batch / aa_stream_append_records, or device-resident (aa_rebase_device_batch, aa_reencode_device_batch: its 80-byte macroblock
  * records are copied back for the first partition, its blocks never leave HBM) -- becomes a VP8 frame in `out`.  The DCT partitions are written on the
  * device from the records where they lie, dense or packed (k_serialize_tokens: a lane per job and partition, partition p takes the
  * macroblock rows r % num_dct_partitions == p); meanwhile host workers, one job each, write the frame header and the macroblock headers of

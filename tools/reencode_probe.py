@@ -7,10 +7,14 @@ oracle/_ref/xc-enc -r takes for ONE such frame on one core of the same host: the
 the prediction key frame encoded by the reference, then `xc-enc -r -W -q <quality>` over a one-frame chunk, timed as a process (its
 start-up and its reading of the inputs included: tens of milliseconds beside seconds).  The reference is the yardstick.
 
-    python tools/reencode_probe.py [--streams 120] [--copies 4] [--reps 1] [--warmup 0] [--reference] [--out results.json]
+    python tools/reencode_probe.py [--streams 120] [--copies 4] [--reps 1] [--warmup 0] [--reference] [--device] [--out results.json]
+
+--device: per quality, in the same process, the same frames on fresh decoders through aa_reencode_device_batch
+(Context.reencode_as_inter( records=False ): the records compacted on the device and kept there); its figures go under "device" in the
+quality's result, the download leg being the count and row words alone, the host-records leg 0 and the append leg bookkeeping.
 
 Before anything is printed a sample of the decoded new frames is compared with its target (mean absolute luma error).
-profiles/reencode_batch.md holds what was measured."""
+profiles/reencode_batch.md and profiles/reencode_device.md hold what was measured."""
 import argparse
 import collections
 import json
@@ -67,6 +71,7 @@ def main():
     ap.add_argument("--sample", type=int, default=4, help="new frames compared with their targets")
     ap.add_argument("--reference", action="store_true", help="also time oracle/_ref/xc-enc -r on one such frame")
     ap.add_argument("--out", help="also write the results as JSON to this file")
+    ap.add_argument("--device", action="store_true", help="then, per quality, the same frames on fresh decoders through aa_reencode_device_batch (records kept in HBM)")
     args = ap.parse_args()
     import torch
     import workload
@@ -100,7 +105,8 @@ def main():
     b_hdr, b_t = headers * args.copies, targets * args.copies
     nmb = sum(hh["num_macroblocks"] for hh in b_hdr)
     out = {"config": args.config, "frames": n, "macroblocks": nmb, "reps": args.reps, "qualities": {}}
-    for quality in ("best", "rt"):
+
+    def measure(quality, on_device):
         runs, classes = [], collections.Counter()
         for rep in range(args.warmup + args.reps):
             decs = []
@@ -111,16 +117,16 @@ def main():
                     decs.append(d)
             ctx.sync()
             t0 = time.perf_counter()
-            results = ctx.reencode_as_inter(decs, b_hdr, b_t, quality=quality)
+            results = ctx.reencode_as_inter(decs, b_hdr, b_t, quality=quality, records=not on_device)
             wall_py = (time.perf_counter() - t0) * 1e3
             timing = ctx.reencode_timing()
             timing["python_call_ms"] = wall_py
-            timing["coeff_blocks"] = sum(len(r[2]) for r in results)
+            timing["coeff_blocks"] = sum(r[1] if on_device else len(r[2]) for r in results)
             fis = [r[0] for r in results]
             ctx.decode_batch(decs, fis)
             if rep == args.warmup + args.reps - 1:
-                for r in results[:len(paths)]:
-                    ym, cnt = np.unique(r[1]["y_mode"], return_counts=True)
+                for d, r in zip(decs[:len(paths)], results[:len(paths)]):
+                    ym, cnt = np.unique(d.read_records(r[0])[1]["y_mode"] if on_device else r[1]["y_mode"], return_counts=True)
                     for m, k in zip(ym, cnt):
                         classes[MODES[m]] += int(k) * args.copies
                 for k in np.linspace(0, n - 1, args.sample).astype(int):
@@ -132,19 +138,27 @@ def main():
             del results, decs
             if rep >= args.warmup:
                 runs.append(timing)
-            print("reencode_probe: -q %s, repetition %d: call %.1f ms" % (quality, rep, timing["call_ms"]), file=sys.stderr, flush=True)
+            print("reencode_probe: -q %s%s, repetition %d: call %.1f ms" % (quality, ", records kept on the device" if on_device else "", rep, timing["call_ms"]), file=sys.stderr, flush=True)
         mean = {k: float(np.mean([r[k] for r in runs])) for k in ("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms", "python_call_ms")}
         q = {"runs": runs, "mean": mean, "classes": dict(classes), "macroblocks_per_s_call": nmb / mean["call_ms"] * 1e3,
              "frames_per_s_call": n / mean["call_ms"] * 1e3, "ms_per_frame": mean["call_ms"] / n, "share_kernel": mean["kernels_ms"] / mean["call_ms"]}
-        if args.reference:
+        if args.reference and not on_device:
             s = reference_seconds(size[0], size[1], display[0], display[1], headers[0]["q_index"], quality)
             q["reference_s_per_frame_one_core"] = s
             if s:
                 q["reference_frames_per_s_one_core"] = 1.0 / s
-        out["qualities"][quality] = q
-        print("re-encode -q %s of %d frames (%d macroblocks): call %.1f ms = up + kernel %.1f, download %.1f, host records %.1f, append %.1f; %.2f ms a frame, %.0f frames/s%s; %s"
-              % (quality, n, nmb, mean["call_ms"], mean["kernels_ms"], mean["download_ms"], mean["records_ms"], mean["append_ms"], q["ms_per_frame"], q["frames_per_s_call"],
+        print("re-encode -q %s%s of %d frames (%d macroblocks): call %.1f ms = up + kernel%s %.1f, download %.1f, host records %.1f, append %.1f; %.2f ms a frame, %.0f frames/s%s; %s"
+              % (quality, ", records kept on the device," if on_device else "", n, nmb, mean["call_ms"], "s" if on_device else "", mean["kernels_ms"], mean["download_ms"],
+                 mean["records_ms"], mean["append_ms"], q["ms_per_frame"], q["frames_per_s_call"],
                  "; xc-enc -r on one core: %.2f s a frame" % q["reference_s_per_frame_one_core"] if q.get("reference_s_per_frame_one_core") else "", dict(classes)), flush=True)
+        return q
+
+    for quality in ("best", "rt"):
+        out["qualities"][quality] = measure(quality, False)
+        if args.device:
+            q = out["qualities"][quality]["device"] = measure(quality, True)
+            q["coeff_blocks_equal_host_path"] = q["runs"][-1]["coeff_blocks"] == out["qualities"][quality]["runs"][-1]["coeff_blocks"]
+            q["classes_equal_host_path"] = q["classes"] == out["qualities"][quality]["classes"]
     print(json.dumps(out))
     if args.out:
         with open(args.out, "w") as f:
