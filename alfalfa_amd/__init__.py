@@ -11,5 +11,5 @@ import os as _os
 # HIP user of the process starts the runtime.  A value already in the environment is left alone.
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
-from .decoder import AlfalfaError, Context, Decoder, FilePlayer, Parser, Quality, psnr, read_ivf, serialize_host  # noqa: F401
+from .decoder import AlfalfaError, Context, Decoder, FilePlayer, Parser, Quality, psnr, read_ivf, serialize_host, with_zero_lf_deltas  # noqa: F401
 from .capi import quant_factors  # noqa: F401

@@ -141,6 +141,14 @@ class ReencodeDeviceJob(C.Structure):
                 ("num_coeff_blocks", C.c_uint32), ("num_intra_mbs", C.c_uint32), ("frame_index", C.c_int)]
 
 
+AA_LF_MEASURE_SSIM, AA_LF_MEASURE_SSE = 0, 1
+
+
+class LfSearchJob(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("frame_index", C.c_int), ("original", QualityRef), ("level_lo", C.c_int), ("level_hi", C.c_int),
+                ("best_level", C.c_int), ("evaluated", C.c_int), ("best_score", C.c_double)]
+
+
 class AlfalfaError(RuntimeError):
     """Mirrors the reference's exception types (exception.hh:76-98) by name in `.kind`."""
 
@@ -203,6 +211,8 @@ SYMBOLS = [
     ("aa_reencode_device_batch", C.c_int, [_P, C.POINTER(ReencodeDeviceJob), C.c_int]),
     ("aa_reencode_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_ctx_set_reencode_slots", C.c_int, [_P, C.c_int]),
+    ("aa_lf_search_decode_batch", C.c_int, [_P, C.POINTER(LfSearchJob), C.c_int, C.c_int]),
+    ("aa_ctx_set_lf_search_round", C.c_int, [_P, C.c_int, C.c_int]), ("aa_lf_search_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_parser_last_header_ext", C.c_int, [_P, C.POINTER(FrameHeaderExt)]), ("aa_stream_last_header_ext", C.c_int, [_P, C.POINTER(FrameHeaderExt)]),
     ("aa_parser_last_sub_modes", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]), ("aa_stream_last_sub_modes", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("aa_serialize_host", C.c_int, [C.POINTER(FrameHeader), C.POINTER(FrameHeaderExt), _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include "../../include/alfalfa_amd.h"
+#include "lf_choose.hh"
 
 // One decoded-frame job, resident in HBM (one per (stream, frame)); built by the host when the frame is
 // parsed: raster slots are assigned then (References bookkeeping = Frame::copy_to, frame.cc:271-307), so a
@@ -125,6 +126,26 @@ struct aa_serialize_dev_job {
 #define AA_SERIALIZE_COUNTS ( 2112 + 8 )
 #define AA_SERIALIZE_UPDATES ( 2112 + 8 )
 
+// One job of a slice of the batched loop-filter level search (aa_lf_search_decode_batch), the same over all of its rounds: the frame's own
+// job record (rasters bound: cur[] is the unfiltered reconstruction, three planes back to back; mbs its records) and where its candidates
+// lie: candidate c of a round at cand + c * per, raster | records (records_off) | job record (job_off).
+#define AA_LF_MAX_ROUND 8      // levels per job and round
+struct aa_lf_search_dev_job {
+  aa_dev_frame * frame;
+  uint8_t * cand;
+  uint64_t per;                // bytes
+  uint32_t raster_bytes, luma_bytes, chroma_bytes;     // multiples of 16
+  uint32_t records_off, job_off;
+  uint32_t nmb;
+  uint32_t pw, ph;             // the padded luma plane (measure 1 divides by it)
+  int32_t level_hi;
+  uint32_t pad;
+  aa::LfSegments seg;          // the level of a macroblock by its segment (lf_choose.hh)
+};
+// One entry of a round's table: job `job` of the slice tries the levels first_level .. first_level + n - 1; their scores are
+// [score_off, score_off + n) of the round's score arrays
+struct aa_lf_round_entry { uint32_t job; int32_t first_level; uint32_t n; uint32_t score_off; };
+
 #define AA_MAX_XCD 16
 
 #define AA_SYNC_WS_DUMP 140
@@ -207,6 +228,12 @@ int launch_gather_rasters( const aa_gather_job * jobs, int n, uint8_t * staging,
 int launch_render_rgb( const aa_rgb_job * jobs, int n, int format, const uint32_t * table, uint32_t max_threads, void * stream );
 // dst = src with lf_level := byte `segment_id` of `levels` (records are 80 bytes, 16-byte aligned)
 int launch_lf_relevel( const aa_mb_info * src, aa_mb_info * dst, unsigned nmb, uint32_t levels, void * stream );
+// lf_search_kernels.hip (see there): a round's candidates -- rasters, re-levelled records, job records -- from its table; the rule continued over
+// the round's scores (measure 0: ssim; 1: made from sse); the chosen level into every job's own records and job record
+int launch_lf_candidates( const aa_lf_search_dev_job * jobs, const aa_lf_round_entry * entries, int n_entries, uint32_t max_raster_bytes, void * stream );
+int launch_lf_choose( const aa_lf_search_dev_job * jobs, const aa_lf_round_entry * entries, int n_entries, const double * ssim, const unsigned long long * sse, int measure,
+                      LfChoice * states, void * stream );
+int launch_lf_finish( const aa_lf_search_dev_job * jobs, const LfChoice * states, int n_jobs, uint32_t max_mbs, void * stream );
 // hash_kernels.hip: job i (hash_chain.hh; n of them, longest first) is walked by lane i % lanes_per_wave of wave i / lanes_per_wave; its
 // result goes to results[job.out_index] (out_index < n)
 struct HashJob;

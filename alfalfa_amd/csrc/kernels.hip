@@ -1736,8 +1736,7 @@ __global__ __launch_bounds__( 256 ) void k_lf_relevel( const aa_mb_info * src, a
   const uint4 * s = reinterpret_cast<const uint4 *>( src + i );
   uint4 * d = reinterpret_cast<uint4 *>( dst + i );
   uint4 head = s[0];                                              // y_mode uv_mode ref_frame segment_id | flags lf_level ...
-  const uint32_t seg = ( head.x >> 24 ) & 3u;
-  head.y = ( head.y & 0xFFFF00FFu ) | ( ( ( levels >> ( 8 * seg ) ) & 255u ) << 8 );
+  head.y = aa::lf_relevel_word( head.x, head.y, levels );      // (lf_choose.hh: the statement k_lf_candidates and k_lf_finish share)
   d[0] = head;
   for ( int k = 1; k < 5; k++ ) d[k] = s[k];
 }

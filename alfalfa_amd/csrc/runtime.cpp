@@ -46,7 +46,7 @@
 #include "reencode_compact.hh"
 #include "serializer.hh"
 
-// ONE translation unit, this file and the fourteen it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
+// ONE translation unit, this file and the fifteen it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
 // the pieces share file-local state (the anonymous-namespace helpers, g_last_error) and are #included in dependency order.
 #include "runtime_types.inc"
 #include "runtime_pool.inc"
@@ -59,6 +59,7 @@
 #include "runtime_hashes.inc"
 #include "runtime_quality.inc"
 #include "runtime_lf_search.inc"
+#include "runtime_lf_batch.inc"
 #include "runtime_rebase.inc"
 #include "runtime_reencode.inc"
 #include "runtime_serialize.inc"

@@ -214,7 +214,7 @@ static void ctx_free( aa_ctx * ctx )
   (void) hipEventDestroy( ctx->upload_done );
   if ( ctx->last_raster_download ) (void) hipEventDestroy( ctx->last_raster_download );
   hash_free( ctx );
-  for ( JobRing * r : { &ctx->bind_ring, &ctx->gather_ring, &ctx->rgb_ring, &ctx->quality_ring, &ctx->rebase_ring } ) r->destroy();
+  for ( JobRing * r : { &ctx->bind_ring, &ctx->gather_ring, &ctx->rgb_ring, &ctx->quality_ring, &ctx->rebase_ring, &ctx->lf_ring } ) r->destroy();
   for ( hipEvent_t e : ctx->gather_copied ) if ( e ) (void) hipEventDestroy( e );
   for ( hipEvent_t e : { ctx->rgb_consumer_ev, ctx->quality_consumer_ev } ) if ( e ) (void) hipEventDestroy( e );
   if ( ctx->ws ) (void) hipFree( ctx->ws );

@@ -247,7 +247,10 @@ struct DecodeMark {
 };
 } // namespace
 
-aa_status aa_decode_batch( aa_ctx * ctx, aa_stream * const * streams, int n, const int * frame_index )
+// aa_decode_batch.  hold_filter (null: nobody's): frame i with hold_filter[i] set is reconstructed but NOT loop-filtered -- its level is
+// still being searched (aa_lf_search_decode_batch, which filters it in place once the level is known); everything else of the frame's
+// decode -- raster, References, next_submit -- is done as for any frame.
+static aa_status decode_batch_held( aa_ctx * ctx, aa_stream * const * streams, int n, const int * frame_index, const uint8_t * hold_filter )
 {
   if ( !ctx || !streams || !frame_index || n <= 0 ) return fail( AA_ERR_ARGUMENT, "aa_decode_batch: bad argument" );
   if ( aa_status st = set_device( ctx ) ) return st;
@@ -306,7 +309,7 @@ aa_status aa_decode_batch( aa_ctx * ctx, aa_stream * const * streams, int n, con
     const aa_frame_header & h = r.hdr;
     if ( h.num_intra_mbs < h.num_macroblocks ) { inter_jobs.push_back( r.dev_job ); any_split = any_split || r.has_split; }
     if ( h.has_intra_mb ) { intra_jobs.push_back( r.dev_job ); intra_recs.push_back( &r ); }
-    if ( h.loop_filter_level ) { lf_jobs.push_back( r.dev_job ); lf_geometry.push_back( ( static_cast<uint32_t>( h.mb_width ) << 16 ) | h.mb_height ); }
+    if ( h.loop_filter_level && !( hold_filter && hold_filter[i] ) ) { lf_jobs.push_back( r.dev_job ); lf_geometry.push_back( ( static_cast<uint32_t>( h.mb_width ) << 16 ) | h.mb_height ); }
     if ( i > 0 && ( h.mb_width != streams[0]->frames[frame_index[0]].hdr.mb_width || h.mb_height != streams[0]->frames[frame_index[0]].hdr.mb_height ) ) same_geometry = false;
     max_mbs = std::max<unsigned>( max_mbs, h.num_macroblocks );
     max_mbw = std::max<int>( max_mbw, h.mb_width ); max_mbh = std::max<int>( max_mbh, h.mb_height );
@@ -392,6 +395,11 @@ aa_status aa_decode_batch( aa_ctx * ctx, aa_stream * const * streams, int n, con
   }
   advance.ok = true;
   return AA_OK;
+}
+
+aa_status aa_decode_batch( aa_ctx * ctx, aa_stream * const * streams, int n, const int * frame_index )
+{
+  return decode_batch_held( ctx, streams, n, frame_index, nullptr );
 }
 
 aa_status aa_stream_decode( aa_stream * s, const uint8_t * data, size_t size, int * frame_index, int * shown )

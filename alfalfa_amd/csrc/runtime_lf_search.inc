@@ -5,17 +5,24 @@ namespace {
 // The reference's choice (encoder.cc:489-503): ascending levels, the first one that does not improve on the best so far ends the search.
 void choose_level( const double * q, int n, int level_lo, int * best, double * best_q )
 {
-  *best = level_lo; *best_q = -1.0;
-  for ( int i = 0; i < n && q[i] > *best_q; i++ ) { *best = level_lo + i; *best_q = q[i]; }
+  // (the rule itself: lf_choose.hh, shared with k_lf_choose -- all n scores as one round)
+  aa::LfChoice c;
+  aa::lf_choice_begin( c, level_lo );
+  aa::lf_choice_round( c, level_lo, q, n, level_lo + n - 1 );
+  *best = c.best_level; *best_q = c.best_score;
+}
+// what lf_segment_levels (lf_choose.hh) reads of a stream's segmentation
+aa::LfSegments lf_segments_of( const aa::SegmentationState & seg, bool enabled )
+{
+  aa::LfSegments s;
+  std::memset( &s, 0, sizeof s );
+  s.enabled = enabled; s.absolute = seg.absolute;
+  for ( int k = 0; k < 4; k++ ) s.lf[k] = seg.lf[k];
+  return s;
 }
 uint32_t segment_levels( const aa::SegmentationState & seg, int level )      // frame.cc:144-166 + the clamp of macroblock.cc:611-623
 {
-  uint32_t word = 0;
-  for ( int k = 0; k < 4; k++ ) {
-    const int v = level ? ( seg.enabled ? seg.lf[k] + ( seg.absolute ? 0 : level ) : level ) : 0;
-    word |= static_cast<uint32_t>( v <= 0 ? 0 : ( v > 63 ? 63 : v ) ) << ( 8 * k );
-  }
-  return word;
+  return aa::lf_segment_levels( lf_segments_of( seg, seg.enabled ), level );
 }
 
 // What a search holds until it returns: its scratch decoders and device memory, which work queued on the compute stream may still use.

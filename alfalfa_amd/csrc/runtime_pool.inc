@@ -172,6 +172,25 @@ void dev_free_compute( aa_ctx * ctx, uint8_t * p, size_t bytes )
   }
   dev_free( ctx, p, bytes, true );
 }
+// A piece that got a device allocation of its own (more than half a slab) and that nothing queued uses any more -- the caller has waited
+// for the compute stream -- goes back to the DEVICE, not to a free list: a transient of gigabytes that few later calls ask for again must
+// not stay parked in a context that decodes near its memory limit.  A smaller piece takes the compute-stream route.
+void dev_release_transient( aa_ctx * ctx, uint8_t * p, size_t bytes )
+{
+  if ( !p ) return;
+  const size_t cls = pool_size_class( bytes );
+  if ( cls > kSlabBytes / 2 ) {
+    std::lock_guard<std::mutex> g( ctx->pool_mu );
+    auto it = std::find( ctx->dev_slabs.begin(), ctx->dev_slabs.end(), p );
+    if ( it != ctx->dev_slabs.end() ) {
+      ctx->dev_slabs.erase( it );
+      ctx->pool_bytes -= cls;
+      (void) hipFree( p );
+      return;
+    }
+  }
+  dev_free_compute( ctx, p, bytes );
+}
 // ... and an allocation whose first use is queued on the compute stream
 aa_status dev_alloc_compute( aa_ctx * ctx, size_t bytes, uint8_t ** out )
 {

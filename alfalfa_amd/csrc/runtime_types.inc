@@ -231,7 +231,11 @@ struct aa_ctx {
   double reencode_timing[5] = {};           // aa_reencode_last_timing
   double serialize_timing[5] = {};          // aa_serialize_last_timing
   int reenc_slots = 16;                     // macroblocks of an anti-diagonal per round of k_reencode_inter (aa_ctx_set_reencode_slots)
-  JobRing rebase_ring;                      // the job table and input records of a rebase slice (aa_rebase_batch), copied on the compute stream into the slice's piece
+  int lf_round = 4;                         // aa_lf_search_decode_batch: levels per job and round; lf_jobs_per_slice: jobs per slice, 0 = by memory (aa_ctx_set_lf_search_round)
+  int lf_jobs_per_slice = 0;
+  double lf_timing[8] = {};                 // aa_lf_search_last_timing
+  JobRing lf_ring;                          // a slice's job table, states and round tables of aa_lf_search_decode_batch, copied on the compute stream into the slice's piece
+  JobRing rebase_ring;                     // the job table and input records of a rebase slice (aa_rebase_batch), copied on the compute stream into the slice's piece
   hipEvent_t rgb_consumer_ev = nullptr, quality_consumer_ev = nullptr;   // stream_waits_for: the caller's stream and the compute stream waiting for each other
   // batched hashes (runtime_hashes.inc): a stream of their own, a ring of pinned tables (result table, job table, segment maps: read
   // and written by k_hash_chains over the bus; an entry is its call's until hash_commit_oldest has read the results out of it) and the

@@ -605,6 +605,53 @@ class Context:
         """Macroblocks of an anti-diagonal per round of the re-encode kernel (aa_ctx_set_reencode_slots: 1..16, default 16)."""
         capi.check(self.L.aa_ctx_set_reencode_slots(self.h, int(slots)))
 
+    LF_MEASURES = {"ssim": capi.AA_LF_MEASURE_SSIM, "sse": capi.AA_LF_MEASURE_SSE}
+
+    def lf_search_decode(self, decoders, frame_indices, originals, level_lo=0, level_hi=63, measure="ssim"):
+        """The loop-filter level search of appended frames, and their decode (aa_lf_search_decode_batch; the last statement of
+        Encoder::reencode_as_interframe): frame frame_indices[i] is decoders[i]'s next frame to decode, held as records (append_records,
+        rebase, reencode_as_inter, with records on the host or on the device) under any provisional level.  originals[i]: the target the
+        frame stands for, as reencode_as_inter takes it (the luma plane is read).  level_lo / level_hi: one for all jobs or one per job.
+        measure: "ssim" (x264's SSIM of the padded luma, Context.quality's value) or "sse" (1 - mean squared error / 255^2).
+        -> per job (best_level, best_score, evaluated); afterwards every frame is decoded, filtered with its best level, and its
+        records and stored header carry that level (serialise it with with_zero_lf_deltas( ext ) and the level in the header).
+        Synchronous."""
+        import torch
+        n = len(decoders)
+        if len(frame_indices) != n or len(originals) != n:
+            raise ValueError("lf_search_decode: need as many frame indices and originals as decoders")
+        if measure not in self.LF_MEASURES:
+            raise ValueError("lf_search_decode: measure is \"ssim\" or \"sse\", not %r" % (measure,))
+        los = list(level_lo) if isinstance(level_lo, (list, tuple)) else [level_lo] * n
+        his = list(level_hi) if isinstance(level_hi, (list, tuple)) else [level_hi] * n
+        if len(los) != n or len(his) != n:
+            raise ValueError("lf_search_decode: level_lo / level_hi are one for all jobs or one per job")
+        jobs = (capi.LfSearchJob * max(n, 1))()
+        keep = []
+        for i, (d, t) in enumerate(zip(decoders, originals)):
+            t = self._target_planes("lf_search_decode", i, d, t)
+            j = jobs[i]
+            j.stream, j.frame_index, j.level_lo, j.level_hi = d.h, int(frame_indices[i]), int(los[i]), int(his[i])
+            j.original.y, j.original.u, j.original.v = t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr()
+            j.original.y_stride, j.original.uv_stride = t[0].stride(0), t[1].stride(0)
+            keep.append(t)
+        if n:
+            torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()      # (the originals are ready; the call itself waits for its kernels)
+        capi.check(self.L.aa_lf_search_decode_batch(self.h, jobs, n, self.LF_MEASURES[measure]))
+        return [(jobs[i].best_level, jobs[i].best_score, jobs[i].evaluated) for i in range(n)]
+
+    def set_lf_search_round(self, levels, jobs_per_slice=0):
+        """Levels per job and round of lf_search_decode (1..8, default 4) and jobs per slice (0: by memory) -- aa_ctx_set_lf_search_round."""
+        capi.check(self.L.aa_ctx_set_lf_search_round(self.h, int(levels), int(jobs_per_slice)))
+
+    def lf_search_timing(self):
+        """The last lf_search_decode of this context (aa_lf_search_last_timing), ms: the call (wall clock), then by HIP events the
+        unfiltered reconstruction, k_lf_candidates, the candidates' loop filter, the scoring, k_lf_choose with the states coming down,
+        k_lf_finish with the final filter; and the number of rounds."""
+        out = (C.c_double * 8)()
+        capi.check(self.L.aa_lf_search_last_timing(self.h, out))
+        return dict(zip(("call_ms", "reconstruct_ms", "candidates_ms", "filter_ms", "score_ms", "choose_ms", "finish_ms", "rounds"), out))
+
     def _hash_streams(self, what, decoders):
         n = len(decoders)
         if n == 0:
@@ -825,6 +872,11 @@ class Decoder:
                                               C.byref(best), C.byref(q), qs, rasters.ctypes.data_as(C.c_void_p) if want_rasters else None))
         return best.value, q.value, list(qs), ([rasters[i * rb:(i + 1) * rb].tobytes() for i in range(n)] if want_rasters else None)
 
+    def lf_search_decode(self, frame_index, original, level_lo=0, level_hi=63, measure="ssim"):
+        """This decoder's next frame searched for its loop-filter level and decoded (Context.lf_search_decode)
+        -> (best_level, best_score, evaluated)."""
+        return self.ctx.lf_search_decode([self], [frame_index], [original], level_lo, level_hi, measure)[0]
+
     def release_before(self, first_kept):
         capi.check(self.L.aa_stream_release_before(self.h, first_kept))
 
@@ -906,6 +958,18 @@ class Decoder:
     def import_reference_host(self, y, u, v):
         y, u, v = (np.ascontiguousarray(p, dtype=np.uint8) for p in (y, u, v))
         capi.check(self.L.aa_stream_import_reference_host(self.h, y.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)))
+
+
+def with_zero_lf_deltas(ext):
+    """A header extension (dict, as Parser.header_ext returns it) that writes the loop-filter adjustments as the reference's encoder
+    leaves them after its level search (encoder.cc:464-470): lf_delta_update 1, every reference and mode delta present and zero.  What a
+    frame searched by lf_search_decode is serialised with -- together with filter_adjustments_enabled = 1 and the chosen level in the
+    header; the decoder that parses those bytes then filters with the level alone.  -> a new dict."""
+    out = dict(ext)
+    out["lf_delta_update"] = 1
+    out["ref_lf_update"], out["mode_lf_update"] = [1] * 4, [1] * 4
+    out["ref_lf_delta"], out["mode_lf_delta"] = [0] * 4, [0] * 4
+    return out
 
 
 def psnr(sse, width, height, planes):

@@ -601,6 +601,56 @@ aa_status aa_reencode_last_timing( aa_ctx * ctx, double out[5] );
  * context creation): with a small cap the several-rounds-per-diagonal path runs on a small frame (tests). */
 aa_status aa_ctx_set_reencode_slots( aa_ctx * ctx, int slots );
 
+/* THE LOOP-FILTER LEVEL OF APPENDED FRAMES, searched for a whole batch (the last statement of Encoder::reencode_as_interframe,
+ * reencode.cc:126: apply_best_loopfilter_settings, encoder.cc:459-516) -- and the DECODE of those frames.  Job i's frame is its stream's
+ * next frame to decode, held as records: appended by aa_stream_append_records, aa_reencode_batch, aa_rebase_batch, or device-resident
+ * (aa_reencode_device_batch, aa_rebase_device_batch), with whatever provisional level in its header.  All frames are reconstructed once,
+ * unfiltered (aa_decode_batch's launches, the loop filter held back); then the jobs move together in rounds of K consecutive levels
+ * (aa_ctx_set_lf_search_round; 4): k_lf_candidates copies every searching job's unfiltered raster to K candidate rasters and writes their
+ * re-levelled records and job records, ONE loop-filter launch runs over all candidates, ONE scoring call over their luma planes, and
+ * k_lf_choose continues the reference's rule per job -- levels in ascending order from level_lo, a candidate replaces the best only if its
+ * score is greater, the first that does not ends the search -- so that one small copy per round tells the host who is done.  Level 0 is
+ * scored on the unfiltered raster itself.  At the end the chosen level is set in every job's own records and job record, in place, and
+ * the jobs' own rasters are filtered with it.
+ *   measure   AA_LF_MEASURE_SSIM: x264's SSIM of the padded luma planes, the value aa_quality_batch_async / aa_ssim_host give;
+ *             AA_LF_MEASURE_SSE: 1.0 - ( sse / ( double( pw ) * ph ) ) / ( 255.0 * 255.0 ) from the integer squared error of those planes.
+ *   original  DEVICE; y and y_stride are read: the padded, edge-extended target luma (the re-encode's `target`).
+ *   out       best_level; best_score, its score; evaluated, the candidates the rule consumed (the one that ended the search included).
+ * After the call every job's stream stands where it would stand had the frame been appended with loop_filter_level = best_level,
+ * filter_adjustments_enabled = 1 and zero mode / reference adjustments and then been handed to aa_decode_batch: the raster is the filtered
+ * one, the references are updated, aa_stream_read_records gives lf_level = best_level's level of the record's segment (clamped to 0..63;
+ * a device-resident frame is rewritten in its own piece of HBM, records the host holds too get the same), aa_stream_frame_header carries
+ * the level, release and rewind treat the frame as a decoded one.  The stream's DecoderState is NOT touched: it is the header of the
+ * written frame (aa_serialize_batch: lf_delta_update 1, every ref_lf_update / mode_lf_update 1 with delta 0) that zeroes the adjustments
+ * for whoever parses the bytes.  The results do not depend on K or on how the jobs are sliced.  Synchronous.
+ * Refusals (messages begin "aa_lf_search_decode_batch:"; a refused call decodes nothing, changes no stream and writes no output field):
+ * AA_ERR_ARGUMENT for null pointers, n < 0, levels outside 0 <= lo <= hi <= 63, an unknown measure, a stream of another context or listed
+ * twice, a key frame; AA_ERR_LOGIC for a frame that is not its stream's next to decode or whose records were released;
+ * AA_ERR_UNSUPPORTED under AA_SCHEDULE_DIAGONAL (no row-pipelined loop filter to launch over the candidates).  n == 0 is AA_OK.
+ * A call that FAILS behind its checks (AA_ERR_HIP, AA_ERR_NO_MEMORY: a launch, a copy, the pool, the watchdog; the message names this
+ * call too) may have reconstructed the frames already: they then count as decoded -- next to decode is the frame behind them, the
+ * references are updated -- with the UNFILTERED raster and the provisional level, and no output field is written.  Where the rasters
+ * the frames predict from are still held, aa_stream_rewind_to( stream, frame_index ) and the same call again redo them.
+ * Memory: the scratch of a slice is one piece; a piece of more than 128 MiB is given back to the device when its slice is over (it
+ * does not stay parked in the context's pool), a smaller one is reused by the context's next compute-stream allocation of its size.
+ * (Still AA_ABI_VERSION 4: an addition.) */
+#define AA_LF_MEASURE_SSIM 0
+#define AA_LF_MEASURE_SSE 1
+typedef struct aa_lf_search_job {
+  aa_stream * stream; int frame_index;
+  aa_quality_ref original;
+  int level_lo, level_hi;                          /* 0 <= lo <= hi <= 63 */
+  int best_level, evaluated; double best_score;    /* out */
+} aa_lf_search_job;
+aa_status aa_lf_search_decode_batch( aa_ctx * ctx, aa_lf_search_job * jobs, int n, int measure );
+/* Levels per job and round (1..8, default 4) and jobs per slice (0, the default: as many as an eighth of the memory limit, at most 8 GiB, holds -- the
+ * scratch is jobs x levels x (raster + records + job record)): small numbers take small frames through several rounds and slices (tests). */
+aa_status aa_ctx_set_lf_search_round( aa_ctx * ctx, int levels_per_round, int jobs_per_slice );
+/* Where the last successful aa_lf_search_decode_batch spent its time, ms: out[0] the whole call (wall clock); HIP events on the compute
+ * stream, summed over rounds and slices: [1] the unfiltered reconstruction, [2] round table up and k_lf_candidates, [3] the candidates'
+ * loop filter, [4] the scoring, [5] k_lf_choose and the states down, [6] k_lf_finish and the final filter; [7] the number of rounds. */
+aa_status aa_lf_search_last_timing( aa_ctx * ctx, double out[8] );
+
 /* SERIALISATION (Frame::serialize, serializer.cc:388-829): frame `frame_index` of `stream`, held as records -- parsed from bytes, appended
  * by aa_rebase_batch / aa_reencode_batch / aa_stream_append_records, or device-resident (aa_rebase_device_batch, aa_reencode_device_batch: its 80-byte macroblock
  * records are copied back for the first partition, its blocks never leave HBM) -- becomes a VP8 frame in `out`.  The DCT partitions are written on the
