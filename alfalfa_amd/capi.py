@@ -141,6 +141,8 @@ class ReencodeDeviceJob(C.Structure):
                 ("num_coeff_blocks", C.c_uint32), ("num_intra_mbs", C.c_uint32), ("frame_index", C.c_int)]
 
 
+EncodeJob, EncodeDeviceJob = ReencodeJob, ReencodeDeviceJob       # aa_encode_job / aa_encode_device_job are typedefs of them
+
 AA_LF_MEASURE_SSIM, AA_LF_MEASURE_SSE = 0, 1
 
 
@@ -211,6 +213,9 @@ SYMBOLS = [
     ("aa_reencode_device_batch", C.c_int, [_P, C.POINTER(ReencodeDeviceJob), C.c_int]),
     ("aa_reencode_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_ctx_set_reencode_slots", C.c_int, [_P, C.c_int]),
+    ("aa_encode_batch", C.c_int, [_P, C.POINTER(ReencodeJob), C.c_int]),
+    ("aa_encode_device_batch", C.c_int, [_P, C.POINTER(ReencodeDeviceJob), C.c_int]),
+    ("aa_encode_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_lf_search_decode_batch", C.c_int, [_P, C.POINTER(LfSearchJob), C.c_int, C.c_int]),
     ("aa_ctx_set_lf_search_round", C.c_int, [_P, C.c_int, C.c_int]), ("aa_lf_search_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_parser_last_header_ext", C.c_int, [_P, C.POINTER(FrameHeaderExt)]), ("aa_stream_last_header_ext", C.c_int, [_P, C.POINTER(FrameHeaderExt)]),

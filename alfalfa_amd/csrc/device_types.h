@@ -99,7 +99,7 @@ struct alignas( 16 ) aa_rebase_compact_job {
 // side record per macroblock for the census and the B_PRED trial of its neighbours.
 struct aa_reencode_dev_job {
   aa_rebase_dev_job base;
-  const void * costs;          // aa::ReencCosts (reencode_search.hh)
+  const void * costs;          // aa::ReencCosts; a job of the forward encoder: aa::EncInterCosts or, a key frame, aa::EncKeyCosts (reencode_search.hh)
   aa_mb_info * mbs_out;        // mbw * mbh records: y_mode, uv_mode, ref_frame, nz_mask and u are the kernel's, the rest is zero
   uint32_t * nb;               // [mbw * mbh][4]: aa::ReencNeighbour
   unsigned long long * intra_rows;   // aa_reencode_device_batch: where k_reencode_count leaves the frame's intra-row words (else null, unused)
@@ -252,6 +252,9 @@ int launch_rebase_compact( const aa_rebase_dev_job * jobs, const aa_rebase_compa
 // reencode_kernels.hip: jobs[i] (n of them) -> records, dense coefficients, masks and the unfiltered reconstruction: k_reencode_inter, one
 // workgroup per job; slots: macroblocks of an anti-diagonal a round takes (1..16)
 int launch_reencode( const aa_reencode_dev_job * jobs, int n, int slots, void * stream );
+// encode_kernels.hip: the same over jobs of ONE kind of the forward encoder -- key: k_encode_key (costs = EncKeyCosts, no reference read),
+// otherwise k_encode_inter (costs = EncInterCosts)
+int launch_encode( const aa_reencode_dev_job * jobs, int n, bool key, int slots, void * stream );
 // reencode_compact_kernels.hip, behind launch_reencode on the same stream: the pair of launch_rebase_count / launch_rebase_compact over the
 // records the decision wrote.  k_reencode_count also leaves every frame's intra-row words in jobs[i].intra_rows; k_reencode_compact copies
 // them from there (outs[i].rows) and sets lf_level by lf[i] (aa::HeaderParams, n of them)

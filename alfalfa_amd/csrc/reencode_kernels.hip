@@ -16,72 +16,16 @@
 // kept in LDS.  A slot's own LDS picture (ReencLds) is private to its 16 lanes, so inside a round nothing but wave-level ordering is
 // needed and no slot ever waits for another: slots of one wave run searches of different lengths, and the slot without a macroblock
 // in a round is predicated off -- every wave reaches every barrier.
-#include <hip/hip_runtime.h>
-#include <algorithm>
-
-#include "device_types.h"
-#include "reencode_mb.hh"
+#include "reencode_wave.hh"
 
 namespace aa {
-namespace {
-
-constexpr int kReencSlots = 16;                 // macroblocks of an anti-diagonal in flight: 256 lanes
-
-struct DevLanes {
-  int b;
-  ReencRegs R;
-  template <class F> __device__ __forceinline__ void each( F f ) { f( b, R ); }
-  template <class F> __device__ __forceinline__ uint32_t sum( F f )
-  {
-    uint32_t v = f( b, R );
-#pragma unroll
-    for ( int m = 8; m >= 1; m >>= 1 ) v += static_cast<uint32_t>( __shfl_xor( static_cast<int>( v ), m, 16 ) );
-    return v;
-  }
-  template <class F> __device__ __forceinline__ int32_t sumi( F f )
-  {
-    int32_t v = f( b, R );
-#pragma unroll
-    for ( int m = 8; m >= 1; m >>= 1 ) v += __shfl_xor( v, m, 16 );
-    return v;
-  }
-  // the slot's 16 lanes are one quarter of a wave and run in lock step: what they stored into the slot's LDS picture is ordered for
-  // the wave by program order, the compiler is told not to move LDS accesses across
-  __device__ __forceinline__ void sync()
-  {
-    __builtin_amdgcn_fence( __ATOMIC_RELEASE, "wavefront" );
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence( __ATOMIC_ACQUIRE, "wavefront" );
-  }
-};
-
-} // namespace
 
 // grid.x = job; slots: how many macroblocks of an anti-diagonal a round takes (1..kReencSlots)
 __global__ __launch_bounds__( kReencSlots * 16 ) void k_reencode_inter( const aa_reencode_dev_job * jobs, const int slots )
 {
-  __shared__ ReencLds lds[kReencSlots];
-  const aa_reencode_dev_job & J = jobs[blockIdx.x];
-  const int slot = threadIdx.x >> 4;
-  const int mbw = J.base.mbw, mbh = J.base.mbh;
-  DevLanes lanes;
-  lanes.b = threadIdx.x & 15;
-  const int last = ( mbw - 1 ) + 2 * ( mbh - 1 );
-  for ( int d = 0; d <= last; d++ ) {
-    // rows of the anti-diagonal: col = d - 2 * row in [0, mbw)
-    const int row_lo = d > mbw - 1 ? ( d - ( mbw - 1 ) + 1 ) / 2 : 0, row_hi = std::min( mbh - 1, d / 2 );
-    const int count = row_hi - row_lo + 1;
-    for ( int base = 0; base < count; base += slots ) {
-      const int k = base + slot;
-      if ( slot < slots && k < count ) {
-        const int row = row_lo + k, col = d - 2 * row;
-        ReencMb<DevLanes> mb( lanes, J, lds[slot], static_cast<size_t>( row ) * mbw + col );
-        mb.run();
-      }
-      __threadfence();            // the next rounds' macroblocks read this round's pixels and side records back from memory
-      __syncthreads();
-    }
-  }
+#define AA_WALK_POLICY ReencodePolicy
+#include "reencode_walk.inc"
+#undef AA_WALK_POLICY
 }
 
 int launch_reencode( const aa_reencode_dev_job * jobs, int n, int slots, void * stream )

@@ -27,19 +27,20 @@ struct ReencRegs {
   bool nz, nz2;
 };
 
-template <class Lanes>
+// P: whose decision this is (reencode_search.hh) -- the re-encode's, or the forward encoder's for an inter or a key frame
+template <class Lanes, class P = ReencodePolicy>
 struct ReencMb {
   Lanes & lanes;
   const aa_reencode_dev_job & RJ;
   const aa_rebase_dev_job & J;
-  const ReencCosts & C;
+  const typename P::Costs & C;
   ReencLds & S;
   const size_t mi;
   const int col, row, pw, ph, cw, ch, x0, y0;
   ReencNeighbour above, left;
 
   AA_MHD ReencMb( Lanes & l, const aa_reencode_dev_job & j, ReencLds & s, const size_t m )
-    : lanes( l ), RJ( j ), J( j.base ), C( *static_cast<const ReencCosts *>( j.costs ) ), S( s ), mi( m ), col( static_cast<int>( m % j.base.mbw ) ),
+    : lanes( l ), RJ( j ), J( j.base ), C( *static_cast<const typename P::Costs *>( j.costs ) ), S( s ), mi( m ), col( static_cast<int>( m % j.base.mbw ) ),
       row( static_cast<int>( m / j.base.mbw ) ), pw( j.base.mbw * 16 ), ph( j.base.mbh * 16 ), cw( j.base.mbw * 8 ), ch( j.base.mbh * 8 ), x0( col * 16 ), y0( row * 16 )
   {}
 
@@ -186,9 +187,9 @@ struct ReencMb {
         sse[m] = lanes.sum( [&]( const int b, ReencRegs & R ) { const int d = static_cast<int16_t>( R.s0 - bpred_pixel( m, S.L.edge, b & 3, b >> 2 ) ); return static_cast<uint32_t>( d * d ); } );
       const int above_mode = sb >= 4 ? S.bm[sb - 4] : ( row > 0 ? static_cast<int>( ( above.bm_bottom >> ( 8 * sb ) ) & 0xFFu ) : 0 );
       const int left_mode = ( sb & 3 ) ? S.bm[sb - 1] : ( col > 0 ? static_cast<int>( ( left.bm_right >> ( 8 * ( sb >> 2 ) ) ) & 0xFFu ) : 0 );
-      const uint16_t * mode_costs = C.bmode[above_mode][left_mode];
+      const uint16_t * mode_costs = P::bmode( C, above_mode, left_mode );
       uint32_t best_sse = 0;
-      const int mode = pick_bmode( mode_costs, sse, best_sse );
+      const int mode = pick_bmode<P>( C, mode_costs, sse, best_sse );
       rate += mode_costs[mode];
       distortion += best_sse;
       lanes.sync();                                  // (every lane has read bm[] before lane 0 writes it)
@@ -305,19 +306,25 @@ struct ReencMb {
     above.mv = left.mv = above_left.mv = 0; above_left.bm_bottom = above_left.bm_right = 0; above.bm_bottom = above.bm_right = left.bm_bottom = left.bm_right = 0;
     if ( row > 0 ) above = neighbour( mi - mbw );
     if ( col > 0 ) left = neighbour( mi - 1 );
-    if ( row > 0 && col > 0 ) above_left = neighbour( mi - mbw - 1 );
-    const ReencCensus cen = census( above, left, above_left, C.mv_counts_to_probs, static_cast<unsigned>( col ), static_cast<unsigned>( row ), mbw, mbh );
-    const ReencChoice choice = choose_prediction( *this, C, cen, static_cast<unsigned>( col ), static_cast<unsigned>( row ), mbw, mbh );
+    if constexpr ( !P::kKey ) { if ( row > 0 && col > 0 ) above_left = neighbour( mi - mbw - 1 ); }      // (a key frame takes no census)
+    const ReencCensus cen = [&]() {
+      if constexpr ( P::kKey ) return ReencCensus();
+      else return census( above, left, above_left, P::inter( C ).mv_counts_to_probs, static_cast<unsigned>( col ), static_cast<unsigned>( row ), mbw, mbh );
+    }();
+    const ReencChoice choice = choose_prediction<P>( *this, C, cen, static_cast<unsigned>( col ), static_cast<unsigned>( row ), mbw, mbh );
     const int mode = choice.mode;
-    const bool inter = mode > B_PRED;
+    const bool inter = !P::kKey && mode > B_PRED;
     uint32_t mask;
     int uv_mode = 0;
     if ( mode == B_PRED ) mask = keep_bpred();
     else {
-      lanes.each( [&]( const int b, ReencRegs & R ) { if ( inter ) predict_inter( b, choice.mv.x, choice.mv.y, R.p ); else predict16( mode, b, R.p ); } );
+      lanes.each( [&]( const int b, ReencRegs & R ) {
+        if constexpr ( P::kKey ) predict16( mode, b, R.p );
+        else { if ( inter ) predict_inter( b, choice.mv.x, choice.mv.y, R.p ); else predict16( mode, b, R.p ); } } );
       mask = code_luma_with_y2();
     }
-    mask |= inter ? code_chroma_inter( choice.mv.x, choice.mv.y ) : code_chroma_intra( uv_mode );
+    if constexpr ( !P::kKey ) mask |= inter ? code_chroma_inter( choice.mv.x, choice.mv.y ) : code_chroma_intra( uv_mode );
+    else mask |= code_chroma_intra( uv_mode );
 
     // the record (what the parser would say of the serialised macroblock, but for flags, coeff_index and lf_level: the host's) and
     // the side record for the macroblocks to the right and below

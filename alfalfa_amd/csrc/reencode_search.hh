@@ -6,6 +6,7 @@
 // like vp8_math.hh: host and device compile one source.
 #pragma once
 #include <stdint.h>
+#include <cmath>
 #include <cstring>
 
 #include "cost_tables.h"
@@ -103,8 +104,75 @@ AA_MHD uint32_t motion_vector_cost( const ReencCosts & C, int x, int y, uint32_t
   return static_cast<uint32_t>( ( static_cast<uint64_t>( C.mv_comp[0][y < 0][ay] ) + C.mv_comp[1][x < 0][ax] ) * weight / 128u );
 }
 
+// ---- the three policies of the decision: whose rate model, which multipliers, what a site of the diamond search costs ----
+// EncInterCosts / EncKeyCosts: the cost blocks of the forward encoder (aa_encode_batch; Encoder::encode_raster, encode_inter.cc:577-653,
+// encode_intra.cc:388-456), filled on the host (enc_fill_inter_costs / enc_fill_key_costs).  The multipliers are update_rd_multipliers'
+// (encoder.cc:178-193), per job.
+struct EncInterCosts {
+  ReencCosts base;                  // mode, sub-block mode and vector costs as the re-encode's
+  uint32_t rate_mul, dist_mul;
+  uint32_t sad_per_bit;             // sad_per_bit16lut[y_ac_qi], the weight of a site's rate
+  uint32_t pad;
+  uint16_t mv_sad[256];             // Costs::fill_mv_sad_costs (costs.cc:135-149)
+};
+static_assert( sizeof( EncInterCosts ) % 8 == 0, "EncInterCosts sits in a table of 8-byte aligned pieces" );
+// A key frame reads no probability, no vector cost and no census table: two kilobytes, not ten
+struct EncKeyCosts {
+  uint16_t bmode[10][10][10];       // as ReencCosts'
+  uint16_t mbmode[5];               // mbmode_costs[0][DC_PRED .. B_PRED], from k_kf_y_mode_probs over kKfYModeTree
+  uint16_t pad;
+  uint32_t rate_mul, dist_mul;
+  uint32_t pad2;
+};
+static_assert( sizeof( EncKeyCosts ) % 8 == 0, "EncKeyCosts sits in a table of 8-byte aligned pieces" );
+
+// Costs::sad_motion_vector_cost( mv, MotionVector(), weight ) (costs.cc:231-240)
+AA_MHD uint32_t sad_motion_vector_cost( const uint16_t * mv_sad, int mvx, int mvy, uint32_t weight )
+{
+  int x = mvx >> 2, y = mvy >> 2;
+  x = x > 255 ? 255 : ( x < -255 ? -255 : x ); y = y > 255 ? 255 : ( y < -255 ? -255 : y );
+  return static_cast<uint32_t>( ( ( static_cast<uint64_t>( mv_sad[iabs( y )] ) + mv_sad[iabs( x )] ) * weight + 128u ) / 256u );
+}
+
+// aa_reencode_batch: Encoder::reencode_as_interframe.  Constants 300 / 1; a site of the search costs its SAD (see diamond_search).
+struct ReencodePolicy {
+  using Costs = ReencCosts;
+  static constexpr bool kKey = false;
+  AA_MHD static uint32_t rate_mul( const Costs & ) { return kRateMultiplier; }
+  AA_MHD static uint32_t dist_mul( const Costs & ) { return kDistortionMultiplier; }
+  AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.bmode[above][left]; }
+  AA_MHD static uint32_t mbmode_intra( const Costs & C, int mode ) { return C.mbmode_intra[mode]; }
+  AA_MHD static bool tries_bpred( const Costs & C ) { return C.quality != REENC_REALTIME; }
+  AA_MHD static const ReencCosts & inter( const Costs & C ) { return C; }
+  AA_MHD static uint32_t site_cost( const Costs &, int, int, uint32_t sad ) { return rdcost( 0, sad, 1, 1 ); }
+};
+// aa_encode_batch, an inter frame: encode_raster<InterFrame>.  The job's multipliers; a site costs its SAD and the rate of its vector.
+struct ForwardInterPolicy {
+  using Costs = EncInterCosts;
+  static constexpr bool kKey = false;
+  AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.rate_mul; }
+  AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.dist_mul; }
+  AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.base.bmode[above][left]; }
+  AA_MHD static uint32_t mbmode_intra( const Costs & C, int mode ) { return C.base.mbmode_intra[mode]; }
+  AA_MHD static bool tries_bpred( const Costs & C ) { return C.base.quality != REENC_REALTIME; }
+  AA_MHD static const ReencCosts & inter( const Costs & C ) { return C.base; }
+  AA_MHD static uint32_t site_cost( const Costs & C, int mvx, int mvy, uint32_t sad ) { return rdcost( sad_motion_vector_cost( C.mv_sad, mvx, mvy, C.sad_per_bit ), sad, 1, 1 ); }
+};
+// aa_encode_batch, a key frame: encode_raster<KeyFrame>.  No inter candidate; the B_PRED trial in both qualities (the real-time
+// exclusion, encode_intra.cc:98-102, is the inter frames' alone).
+struct KeyPolicy {
+  using Costs = EncKeyCosts;
+  static constexpr bool kKey = true;
+  AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.rate_mul; }
+  AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.dist_mul; }
+  AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.bmode[above][left]; }
+  AA_MHD static uint32_t mbmode_intra( const Costs & C, int mode ) { return C.mbmode[mode]; }
+  AA_MHD static bool tries_bpred( const Costs & ) { return true; }
+};
+
 // luma_sb_intra_predict (encode_intra.cc:360-386): the ten modes ascending, strict <
-AA_MHD int pick_bmode( const uint16_t * mode_costs, const uint32_t ( &sse )[10], uint32_t & best_sse )
+template <class P = ReencodePolicy>
+AA_MHD int pick_bmode( const typename P::Costs & C, const uint16_t * mode_costs, const uint32_t ( &sse )[10], uint32_t & best_sse )
 {
   uint32_t min_error = kNoCost;
   int best = 0;
@@ -112,7 +180,7 @@ AA_MHD int pick_bmode( const uint16_t * mode_costs, const uint32_t ( &sse )[10],
 #pragma unroll
 #endif
   for ( int m = 0; m < 10; m++ ) {
-    const uint32_t e = rdcost( mode_costs[m], sse[m], kRateMultiplier, kDistortionMultiplier );
+    const uint32_t e = rdcost( mode_costs[m], sse[m], P::rate_mul( C ), P::dist_mul( C ) );
     if ( e < min_error ) { best = m; min_error = e; best_sse = sse[m]; }
   }
   return best;
@@ -190,8 +258,8 @@ struct ReencSearch { Mv mv; int first_step; };
 
 // Encoder::diamond_search (encode_inter.cc:172-229).  The step halves from at most 512 down to 2: nine rounds at the most, written
 // as a counted loop; a round whose step has run out does nothing.  base: best_ref, already clamped (clamping it again changes nothing).
-template <class Px>
-AA_MHD ReencSearch diamond_search( Px & px, const Mv base, Mv origin, int step_size, unsigned col, unsigned row, unsigned mbw, unsigned mbh )
+template <class P = ReencodePolicy, class Px>
+AA_MHD ReencSearch diamond_search( Px & px, const typename P::Costs & C, const Mv base, Mv origin, int step_size, unsigned col, unsigned row, unsigned mbw, unsigned mbh )
 {
   int first_step = step_size / 2;
   for ( int round = 0; round < 9; round++ ) {
@@ -207,10 +275,10 @@ AA_MHD ReencSearch diamond_search( Px & px, const Mv base, Mv origin, int step_s
       Mv at; at.x = static_cast<int16_t>( mv.x + base.x ); at.y = static_cast<int16_t>( mv.y + base.y );
       at = clamp_mv( at, col, row, mbw, mbh );
       const uint32_t sad = px.inter_sad( at.x, at.y );
-      // rdcost( sad_motion_vector_cost( mv, 0, sad_per_bit16lut[y_ac_qi] ), SAD, 1, 1 ): the rate is ZERO on this path.  Costs is value-
-      // initialised (encoder.cc:77,86) and fill_mv_sad_costs is encode_raster's alone (encode_inter.cc:602), which a re-encode never
-      // runs, so every entry of mv_sad_costs is 0 and ( 0 * weight + 128 ) / 256 = 0: a site costs its SAD.
-      const uint32_t cost = rdcost( 0, sad, 1, 1 );
+      // rdcost( sad_motion_vector_cost( mv, 0, sad_per_bit16lut[y_ac_qi] ), SAD, 1, 1 ).  On the RE-ENCODE's path the rate is ZERO: Costs is
+      // value-initialised (encoder.cc:77,86) and fill_mv_sad_costs is encode_raster's alone (encode_inter.cc:602), which a re-encode never
+      // runs, so every entry of mv_sad_costs is 0 and ( 0 * weight + 128 ) / 256 = 0: a site costs its SAD.  The forward encoder fills it.
+      const uint32_t cost = P::site_cost( C, mv.x, mv.y, sad );
       if ( cost < best_cost ) { best_cost = cost; best = mv; }
     }
     if ( best == origin ) first_step = step_size / 2;
@@ -223,15 +291,15 @@ AA_MHD ReencSearch diamond_search( Px & px, const Mv base, Mv origin, int step_s
 
 // The NEWMV search of luma_mb_inter_predict (encode_inter.cc:287-300): diamond_search again from where it ended, with the step it
 // returned, until the vector no longer moves.  The returned step at least halves every time: nine searches at the most.
-template <class Px>
-AA_MHD Mv newmv_search( Px & px, const Mv best_ref, unsigned col, unsigned row, unsigned mbw, unsigned mbh )
+template <class P = ReencodePolicy, class Px>
+AA_MHD Mv newmv_search( Px & px, const typename P::Costs & C, const Mv best_ref, unsigned col, unsigned row, unsigned mbw, unsigned mbh )
 {
   Mv mv;
   int step = 512;
   bool done = false;
   for ( int search = 0; search < 9; search++ ) {
     if ( done || step <= 1 ) continue;
-    const ReencSearch r = diamond_search( px, best_ref, mv, step, col, row, mbw, mbh );
+    const ReencSearch r = diamond_search<P>( px, C, best_ref, mv, step, col, row, mbw, mbh );
     if ( r.mv == mv ) { done = true; continue; }
     mv = r.mv;
     step = r.first_step;
@@ -248,39 +316,43 @@ struct ReencChoice { int mode; Mv mv; };
 //                                     the sub-blocks' SSE against the PREDICTION
 //   intra_variance( mode )            variance of target - 16x16 prediction
 //   inter_sad / inter_variance( x, y ) of target - the luma prediction from LAST at that vector
-template <class Px>
-AA_MHD ReencChoice choose_prediction( Px & px, const ReencCosts & C, const ReencCensus & cen, unsigned col, unsigned row, unsigned mbw, unsigned mbh )
+template <class P = ReencodePolicy, class Px>
+AA_MHD ReencChoice choose_prediction( Px & px, const typename P::Costs & C, const ReencCensus & cen, unsigned col, unsigned row, unsigned mbw, unsigned mbh )
 {
   uint32_t best_cost = kNoCost;
   ReencChoice best; best.mode = DC_PRED;
-  // ---- intra: B_PRED first (best quality only), then TM, H, V, DC ----
-  if ( C.quality != REENC_REALTIME ) {
+  const uint32_t rate_mul = P::rate_mul( C ), dist_mul = P::dist_mul( C );
+  // ---- intra: B_PRED first (an inter frame: best quality only), then TM, H, V, DC ----
+  if ( P::tries_bpred( C ) ) {
     uint32_t rate = 0, distortion = 0;
     px.bpred_trial( rate, distortion );
-    const uint32_t cost = rdcost( C.mbmode_intra[B_PRED] + rate, distortion, kRateMultiplier, kDistortionMultiplier );
+    const uint32_t cost = rdcost( P::mbmode_intra( C, B_PRED ) + rate, distortion, rate_mul, dist_mul );
     if ( cost < best_cost ) { best_cost = cost; best.mode = B_PRED; }
   }
   for ( int mode = TM_PRED; mode >= DC_PRED; mode-- ) {
-    const uint32_t cost = rdcost( C.mbmode_intra[mode], px.intra_variance( mode ), kRateMultiplier, kDistortionMultiplier );
+    const uint32_t cost = rdcost( P::mbmode_intra( C, mode ), px.intra_variance( mode ), rate_mul, dist_mul );
     if ( cost < best_cost ) { best_cost = cost; best.mode = mode; }
   }
-  // ---- inter, all from LAST: ZEROMV, NEARESTMV, NEARMV, NEWMV ----
-  const MvRefCosts ref_cost = mv_ref_costs( cen.probs, C.prob_cost );
-  for ( int k = 0; k < 4; k++ ) {
-    Mv mv;
-    int mode = ZEROMV;
-    uint32_t rate = ref_cost.zero;
-    if ( k == 1 ) { mode = NEARESTMV; mv = cen.nearest; rate = ref_cost.nearest; }
-    if ( k == 2 ) { mode = NEARMV; mv = cen.near; rate = ref_cost.near; }
-    if ( k == 3 ) {
-      mode = NEWMV;
-      if ( C.quality == REENC_REALTIME && !( col % 4 == 0 && row % 4 == 0 ) ) continue;
-      mv = newmv_search( px, cen.best, col, row, mbw, mbh );
-      rate = ref_cost.newmv + motion_vector_cost( C, mv.x - cen.best.x, mv.y - cen.best.y, 96 );
+  // ---- inter, all from LAST: ZEROMV, NEARESTMV, NEARMV, NEWMV (a key frame has none) ----
+  if constexpr ( !P::kKey ) {
+    const ReencCosts & I = P::inter( C );
+    const MvRefCosts ref_cost = mv_ref_costs( cen.probs, I.prob_cost );
+    for ( int k = 0; k < 4; k++ ) {
+      Mv mv;
+      int mode = ZEROMV;
+      uint32_t rate = ref_cost.zero;
+      if ( k == 1 ) { mode = NEARESTMV; mv = cen.nearest; rate = ref_cost.nearest; }
+      if ( k == 2 ) { mode = NEARMV; mv = cen.near; rate = ref_cost.near; }
+      if ( k == 3 ) {
+        mode = NEWMV;
+        if ( I.quality == REENC_REALTIME && !( col % 4 == 0 && row % 4 == 0 ) ) continue;
+        mv = newmv_search<P>( px, C, cen.best, col, row, mbw, mbh );
+        rate = ref_cost.newmv + motion_vector_cost( I, mv.x - cen.best.x, mv.y - cen.best.y, 96 );
+      }
+      if ( k != 0 && mv.zero() ) continue;                       // the same as ZEROMV
+      const uint32_t cost = rdcost( rate, px.inter_variance( mv.x, mv.y ), rate_mul, dist_mul );
+      if ( cost < best_cost ) { best_cost = cost; best.mode = mode; best.mv = mv; }
     }
-    if ( k != 0 && mv.zero() ) continue;                       // the same as ZEROMV
-    const uint32_t cost = rdcost( rate, px.inter_variance( mv.x, mv.y ), kRateMultiplier, kDistortionMultiplier );
-    if ( cost < best_cost ) { best_cost = cost; best.mode = mode; best.mv = mv; }
   }
   if ( best.mode <= B_PRED ) best.mv = Mv();
   return best;
@@ -304,6 +376,54 @@ inline void reenc_fill_costs( ReencCosts & C, const uint8_t mv_probs[2][19], int
   }
   std::memcpy( C.mv_counts_to_probs, k_mv_counts_to_probs, 24 );
   C.quality = static_cast<uint8_t>( quality );
+}
+
+// Encoder::update_rd_multipliers (encoder.cc:178-193), in double as written there; y_ac: the quantiser's factor, not its index
+inline void enc_rd_multipliers( uint16_t y_ac, uint32_t & rate_mul, uint32_t & dist_mul )
+{
+  const double q_ac = ( y_ac < 160 ) ? y_ac : 160.0;
+  rate_mul = static_cast<uint32_t>( q_ac * q_ac * 2.80 );
+  if ( rate_mul > 1000 ) { dist_mul = 1; rate_mul /= 100; }
+  else dist_mul = 100;
+}
+
+// sad_per_bit16lut[q_index] (libvpx's table, encode_inter.cc:144-152): the values 2..14, each held for a run of indices
+inline uint32_t enc_sad_per_bit( unsigned q_index )
+{
+  static constexpr uint8_t run[13] = { 16, 14, 12, 12, 12, 12, 12, 12, 8, 6, 6, 4, 2 };
+  unsigned end = 0;
+  for ( unsigned v = 0; v < 13; v++ ) { end += run[v]; if ( q_index < end ) return 2 + v; }
+  return 14;
+}
+
+// Costs::fill_mv_sad_costs (costs.cc:135-149): the expression in float and double as written there, truncated
+inline void enc_fill_mv_sad( uint16_t ( &mv_sad )[256] )
+{
+  mv_sad[0] = 300;
+  for ( size_t i = 1; i <= 255; i++ ) {
+    const size_t cost = 256 * ( 2 * log2f( 8 * i ) + 0.6 );
+    mv_sad[i] = static_cast<uint16_t>( cost );
+  }
+}
+
+// A forward inter job's cost block: the re-encode's (mbmode_costs[1], the stream's current vector probabilities) and what
+// encode_raster<InterFrame> adds (encode_inter.cc:594-602)
+inline void enc_fill_inter_costs( EncInterCosts & C, const uint8_t mv_probs[2][19], int quality, uint16_t y_ac, unsigned q_index )
+{
+  reenc_fill_costs( C.base, mv_probs, quality );
+  enc_rd_multipliers( y_ac, C.rate_mul, C.dist_mul );
+  C.sad_per_bit = enc_sad_per_bit( q_index );
+  C.pad = 0;
+  enc_fill_mv_sad( C.mv_sad );
+}
+
+// A key job's: the sub-block costs and mbmode_costs[0] (Costs::fill_mode_costs)
+inline void enc_fill_key_costs( EncKeyCosts & C, uint16_t y_ac )
+{
+  std::memset( &C, 0, sizeof C );
+  for ( int a = 0; a < 10; a++ ) for ( int l = 0; l < 10; l++ ) tree_costs( C.bmode[a][l], k_kf_b_mode_probs + ( a * 10 + l ) * 9, kBModeTree, k_prob_cost );
+  tree_costs( C.mbmode, k_kf_y_mode_probs, kKfYModeTree, k_prob_cost );
+  enc_rd_multipliers( y_ac, C.rate_mul, C.dist_mul );
 }
 
 } // namespace aa

@@ -62,4 +62,5 @@
 #include "runtime_lf_batch.inc"
 #include "runtime_rebase.inc"
 #include "runtime_reencode.inc"
+#include "runtime_encode.inc"
 #include "runtime_serialize.inc"

@@ -3,7 +3,17 @@
 // built on the host and appended as aa_stream_append_records appends them -- or (aa_reencode_device_batch) compacted on the device into a
 // piece of HBM that is the frame's from then on; kernels in reencode_compact_kernels.hip, the rule in reencode_compact.hh.  Modelled on
 // aa_rebase_batch / aa_rebase_device_batch (runtime_rebase.inc), whose job-table ring, slice bound, piece sizes and record builder it shares.
+// Both entry points are templates over their caller: the re-encode here, the forward encoder in runtime_encode.inc (aa_encode_batch /
+// aa_encode_device_batch), whose jobs may be key frames and whose kernels are k_encode_key / k_encode_inter.
 namespace {
+
+// The re-encode as a caller of reencode_batch / reencode_device_batch.  kForward: jobs may be key frames, inter jobs need a decoded last
+// reference, the cost blocks are the forward policies' (reencode_search.hh), and each kind has its own kernel.
+struct ReencodeCall {
+  static constexpr bool kForward = false;
+  static constexpr const char * kHost = "aa_reencode_batch", * kDevice = "aa_reencode_device_batch";
+  static double * timing( aa_ctx * ctx ) { return ctx->reencode_timing; }
+};
 
 // What the kernel left of a job -> the caller's records: flags, nz_mask and coeff_index by rebase_records, as the parser sets them for
 // the serialised frame; lf_level from the new header (mb_lf_level) with the stream's current filter adjustments; segment_id 0.
@@ -16,7 +26,7 @@ RebaseCounts reencode_records( const aa_mb_info * in, const uint32_t * masks, co
 
 // Job i of a re-encode call (aa_reencode_job or aa_reencode_device_job: stream, hdr, target, quality) against the jobs before it: what
 // both entry points refuse, in one order and one wording.  `who`: the ABI call, in front of the message.
-template <class Job>
+template <class Call, class Job>
 aa_status reencode_check_job( const char * who, aa_ctx * ctx, const Job * jobs, int i )
 {
   const auto no = [who]( aa_status code, int k, const std::string & what ) { return fail( code, std::string( who ) + ": job " + std::to_string( k ) + ": " + what ); };
@@ -25,16 +35,20 @@ aa_status reencode_check_job( const char * who, aa_ctx * ctx, const Job * jobs, 
   aa_stream * s = j.stream;
   if ( s->ctx != ctx ) return no( AA_ERR_ARGUMENT, i, "stream belongs to another context" );
   for ( int k = 0; k < i; k++ ) if ( jobs[k].stream == s ) return no( AA_ERR_ARGUMENT, i, "its stream is also job " + std::to_string( k ) + "'s: one new frame per stream and call" );
-  if ( j.hdr->key_frame ) return no( AA_ERR_ARGUMENT, i, "the new frame's header says key frame: a re-encode makes an inter frame" );
+  const bool key = j.hdr->key_frame != 0;
+  if ( key && !Call::kForward ) return no( AA_ERR_ARGUMENT, i, "the new frame's header says key frame: a re-encode makes an inter frame" );
   if ( j.hdr->segmentation_enabled ) return no( AA_ERR_UNSUPPORTED, i, "segmentation is enabled: the reference refuses it too (reencode.cc:47-49)" );
   if ( j.quality != AA_REENCODE_BEST && j.quality != AA_REENCODE_REALTIME ) return no( AA_ERR_ARGUMENT, i, "quality is neither AA_REENCODE_BEST nor AA_REENCODE_REALTIME" );
   const size_t nmb = size_t( s->parser.mb_width() ) * s->parser.mb_height();
   if ( j.hdr->mb_width != s->parser.mb_width() || j.hdr->mb_height != s->parser.mb_height() || j.hdr->num_macroblocks != nmb )
     return no( AA_ERR_ARGUMENT, i, "the header's macroblock dimensions are not this decoder's" );
-  if ( s->next_submit != static_cast<int>( s->frames.size() ) ) return no( AA_ERR_LOGIC, i, "its stream holds a frame that is appended but not decoded: the references are not current" );
+  // (a key frame predicts from nothing: it needs neither a reference nor a stream whose frames are all decoded)
+  if ( !key && s->next_submit != static_cast<int>( s->frames.size() ) ) return no( AA_ERR_LOGIC, i, "its stream holds a frame that is appended but not decoded: the references are not current" );
   if ( j.target.y_stride < int64_t( s->pw ) || j.target.uv_stride < int64_t( s->pw / 2 ) ) return no( AA_ERR_ARGUMENT, i, "row stride smaller than the padded plane's width" );
   for ( int f = 0; f < 6; f++ ) if ( !j.hdr->quant[0][f] ) return no( AA_ERR_ARGUMENT, i, "a quantiser factor of the header is zero" );
-  if ( s->cur_ref_slot[0] < 0 || !s->slots[s->cur_ref_slot[0]].dev ) return no( AA_ERR_LOGIC, i, "its stream has no reference rasters" );
+  if ( !key && ( s->cur_ref_slot[0] < 0 || !s->slots[s->cur_ref_slot[0]].dev ) ) return no( AA_ERR_LOGIC, i, "its stream has no reference rasters" );
+  if ( Call::kForward && !key && s->slots[s->cur_ref_slot[0]].shared )
+    return no( AA_ERR_LOGIC, i, "its stream has no decoded last reference (the blank raster of a new decoder): an inter frame needs a key frame before it" );
   return AA_OK;
 }
 
@@ -43,16 +57,20 @@ struct ReencodePlaces { uint8_t * costs, * masks, * records, * dense, * side, * 
 
 // What a slice's kernels read of one job, into its entry of the job table, its rate model (the pinned copy of *at.costs) and what
 // mb_lf_level reads of it: the new header's level, the stream's current adjustments where the header keeps them switched on
-template <class Job>
-void reencode_fill_job( aa_reencode_dev_job & d, aa::ReencCosts & costs, aa::HeaderParams & fp, const Job & j, const ReencodePlaces & at )
+template <class Call, class Job>
+void reencode_fill_job( aa_reencode_dev_job & d, void * costs, aa::HeaderParams & fp, const Job & j, const ReencodePlaces & at )
 {
   aa_stream * s = j.stream;
+  const bool key = Call::kForward && j.hdr->key_frame;
   std::memset( &d, 0, sizeof d );
-  for ( int p = 0; p < 3; p++ ) d.base.ref[1][p] = slot_plane( s, s->cur_ref_slot[0], p );          // every candidate predicts from LAST
+  if ( !key ) for ( int p = 0; p < 3; p++ ) d.base.ref[1][p] = slot_plane( s, s->cur_ref_slot[0], p );          // every candidate predicts from LAST
   d.base.target[0] = static_cast<const uint8_t *>( j.target.y ); d.base.target[1] = static_cast<const uint8_t *>( j.target.u ); d.base.target[2] = static_cast<const uint8_t *>( j.target.v );
   d.base.target_stride[0] = j.target.y_stride; d.base.target_stride[1] = j.target.uv_stride;
   // the rate model: the mode costs are constants, the vector costs come from the stream's CURRENT probabilities (reencode.cc:82-84)
-  aa::reenc_fill_costs( costs, s->parser.probs().mv, j.quality );
+  // (the forward encoder adds the job's multipliers and the search's site costs; a key frame's block holds no vector cost at all)
+  if ( !Call::kForward ) aa::reenc_fill_costs( *static_cast<aa::ReencCosts *>( costs ), s->parser.probs().mv, j.quality );
+  else if ( key ) aa::enc_fill_key_costs( *static_cast<aa::EncKeyCosts *>( costs ), j.hdr->quant[0][1] );
+  else aa::enc_fill_inter_costs( *static_cast<aa::EncInterCosts *>( costs ), s->parser.probs().mv, j.quality, j.hdr->quant[0][1], j.hdr->q_index );
   d.costs = at.costs;
   d.base.masks = reinterpret_cast<uint32_t *>( at.masks );
   d.mbs_out = reinterpret_cast<aa_mb_info *>( at.records );
@@ -62,7 +80,37 @@ void reencode_fill_job( aa_reencode_dev_job & d, aa::ReencCosts & costs, aa::Hea
   std::memcpy( d.base.quant, j.hdr->quant[0], sizeof d.base.quant );
   d.base.mbw = j.hdr->mb_width; d.base.mbh = j.hdr->mb_height; d.base.has_intra = 1;
   const aa::FilterAdjustState & fa = s->parser.filter_adjustments();
-  aa::compact::lf_params( fp, j.hdr->loop_filter_level, j.hdr->filter_adjustments_enabled && fa.enabled, fa.ref, fa.mode );
+  // (a key frame resets the stream's adjustments, and aa_frame_header carries no deltas of its own: its level stands unadjusted)
+  aa::compact::lf_params( fp, j.hdr->loop_filter_level, !key && j.hdr->filter_adjustments_enabled && fa.enabled, fa.ref, fa.mode );
+}
+
+// A job's cost block in the slice's upload, and a slice's table order: key jobs first, so that each kernel finds its kind in one run
+template <class Call, class Job>
+size_t reencode_costs_bytes( const Job & j )
+{
+  if ( !Call::kForward ) return align_up( sizeof( aa::ReencCosts ) );
+  return align_up( j.hdr->key_frame ? sizeof( aa::EncKeyCosts ) : sizeof( aa::EncInterCosts ) );
+}
+template <class Call, class Job>
+int reencode_slice_order( const Job * jobs, int first, int count, std::vector<int> & at )
+{
+  at.clear();
+  if ( Call::kForward ) for ( int k = 0; k < count; k++ ) if ( jobs[first + k].hdr->key_frame ) at.push_back( first + k );
+  const int keys = static_cast<int>( at.size() );
+  for ( int k = 0; k < count; k++ ) if ( !( Call::kForward && jobs[first + k].hdr->key_frame ) ) at.push_back( first + k );
+  return keys;
+}
+// The decision over a slice's table: k_reencode_inter, or k_encode_key over its first `keys` entries and k_encode_inter over the rest
+template <class Call>
+aa_status reencode_launch_decision( aa_ctx * ctx, const aa_reencode_dev_job * table, int count, int keys )
+{
+  if ( !Call::kForward ) {
+    if ( int e = aa::launch_reencode( table, count, ctx->reenc_slots, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_reencode_inter" );
+    return AA_OK;
+  }
+  if ( keys ) if ( int e = aa::launch_encode( table, keys, true, ctx->reenc_slots, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_encode_key" );
+  if ( count > keys ) if ( int e = aa::launch_encode( table + keys, count - keys, false, ctx->reenc_slots, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_encode_inter" );
+  return AA_OK;
 }
 
 } // namespace
@@ -76,16 +124,22 @@ aa_status aa_ctx_set_reencode_slots( aa_ctx * ctx, int slots )
   return AA_OK;
 }
 
-aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
+} // extern "C"
+
+namespace {
+
+template <class Call>
+aa_status reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
 {
-  const auto no = []( aa_status code, int i, const std::string & what ) { return fail( code, "aa_reencode_batch: job " + std::to_string( i ) + ": " + what ); };
-  if ( !ctx || !jobs || n <= 0 ) return fail( AA_ERR_ARGUMENT, "aa_reencode_batch: bad argument" );
+  const std::string who = Call::kHost;
+  const auto no = [&who]( aa_status code, int i, const std::string & what ) { return fail( code, who + ": job " + std::to_string( i ) + ": " + what ); };
+  if ( !ctx || !jobs || n <= 0 ) return fail( AA_ERR_ARGUMENT, who + ": bad argument" );
   if ( aa_status st = set_device( ctx ) ) return st;
   // ---- 1. the arguments: nothing is launched, nothing appended unless every job of the call is good ----
   for ( int i = 0; i < n; i++ ) {
     aa_reencode_job & j = jobs[i];
     if ( !j.mbs_out || ( !j.coeffs_out && j.coeff_capacity_blocks ) ) return no( AA_ERR_ARGUMENT, i, "null pointer" );
-    if ( aa_status st = reencode_check_job( "aa_reencode_batch", ctx, jobs, i ) ) return st;
+    if ( aa_status st = reencode_check_job<Call>( Call::kHost, ctx, jobs, i ) ) return st;
     j.num_coeff_blocks = 0; j.frame_index = -1;
   }
 
@@ -96,20 +150,22 @@ aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
   std::vector<uint32_t> intra_mbs( n, 0 );
   for ( int first = 0; first < n; ) {
     int count = 0;
-    size_t dense_total = 0, masks_total = 0, records_total = 0, side_total = 0, raster_total = 0;
+    size_t dense_total = 0, masks_total = 0, records_total = 0, side_total = 0, raster_total = 0, costs_total = 0;
     while ( first + count < n ) {
       const aa_stream * s = jobs[first + count].stream;
       const size_t nmb = size_t( s->parser.mb_width() ) * s->parser.mb_height();
       if ( count && dense_total + nmb * AA_REBASE_MB_BYTES > share ) break;
       dense_total += align_up( nmb * AA_REBASE_MB_BYTES ); masks_total += align_up( nmb * sizeof( uint32_t ) );
       records_total += align_up( nmb * sizeof( aa_mb_info ) ); side_total += align_up( nmb * sizeof( aa::ReencNeighbour ) );
-      raster_total += s->slot_bytes;
+      raster_total += s->slot_bytes; costs_total += reencode_costs_bytes<Call>( jobs[first + count] );
       count++;
     }
+    std::vector<int> at_job;                     // table entry -> job of the call
+    const int keys = reencode_slice_order<Call>( jobs, first, count, at_job );
     // the pinned side: job table | every job's rate model (a JobRing entry, read by one copy); the device piece: the same, then per job
     // masks | records | dense coefficients (the results, downloaded by one copy), then side records and reconstruction rasters
-    const size_t table_bytes = align_up( size_t( count ) * sizeof( aa_reencode_dev_job ) ), costs_bytes = align_up( sizeof( aa::ReencCosts ) );
-    const size_t up_bytes = table_bytes + size_t( count ) * costs_bytes, result_bytes = masks_total + records_total + dense_total;
+    const size_t table_bytes = align_up( size_t( count ) * sizeof( aa_reencode_dev_job ) );
+    const size_t up_bytes = table_bytes + costs_total, result_bytes = masks_total + records_total + dense_total;
     const size_t piece_bytes = up_bytes + result_bytes + side_total + raster_total;
     JobRing::Entry * rb = nullptr;
     if ( aa_status st = ctx->rebase_ring.take( up_bytes, align_up( 64 * sizeof( aa_rebase_dev_job ) ), &rb ) ) return st;
@@ -118,7 +174,7 @@ aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
     struct Back { aa_ctx * c; uint8_t * p; size_t b; ~Back() { dev_free_compute( c, p, b ); } } back { ctx, piece, piece_bytes };
     size_t staging_bytes = 0;
     uint8_t * staging = pinned_get( ctx, result_bytes, &staging_bytes );
-    if ( !staging ) return fail( AA_ERR_HIP, "aa_reencode_batch: pinned staging allocation failed" );
+    if ( !staging ) return fail( AA_ERR_HIP, who + ": pinned staging allocation failed" );
     struct Unpin { aa_ctx * c; uint8_t * p; size_t b; ~Unpin() { std::lock_guard<std::mutex> g( c->pool_mu ); c->pinned_pool.emplace_back( p, b ); } } unpin { ctx, staging, staging_bytes };
 
     aa_reencode_dev_job * table = reinterpret_cast<aa_reencode_dev_job *>( rb->host );
@@ -126,7 +182,7 @@ aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
     std::vector<aa::HeaderParams> lf_params( count );
     size_t up_off = table_bytes, res_off = 0, side_off = up_bytes + result_bytes;
     for ( int k = 0; k < count; k++ ) {
-      const aa_reencode_job & j = jobs[first + k];
+      const aa_reencode_job & j = jobs[at_job[k]];
       aa_stream * s = j.stream;
       const size_t nmb = size_t( s->parser.mb_width() ) * s->parser.mb_height();
       ReencodePlaces at;
@@ -137,17 +193,16 @@ aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
       at.dense = piece + up_bytes + res_off; res_off += align_up( nmb * AA_REBASE_MB_BYTES );
       at.side = piece + side_off; side_off += align_up( nmb * sizeof( aa::ReencNeighbour ) );
       at.raster = piece + side_off; side_off += s->slot_bytes;
-      reencode_fill_job( table[k], *reinterpret_cast<aa::ReencCosts *>( rb->host + up_off ), lf_params[k], j, at );
-      up_off += costs_bytes;
+      reencode_fill_job<Call>( table[k], rb->host + up_off, lf_params[k], j, at );
+      up_off += reencode_costs_bytes<Call>( j );
     }
     hipEvent_t ev[3] = { get_event( ctx ), get_event( ctx ), get_event( ctx ) };      // (aa_reencode_last_timing: tables up + kernel, results down)
     struct Events { aa_ctx * c; hipEvent_t * e; ~Events() { for ( int i = 0; i < 3; i++ ) if ( e[i] ) c->free_events.push_back( e[i] ); } } events { ctx, ev };
-    if ( !ev[0] || !ev[1] || !ev[2] ) return fail( AA_ERR_HIP, "aa_reencode_batch: hipEventCreate failed" );
+    if ( !ev[0] || !ev[1] || !ev[2] ) return fail( AA_ERR_HIP, who + ": hipEventCreate failed" );
     HIP_TRY( hipEventRecord( ev[0], ctx->compute ) );
     HIP_TRY( hipMemcpyAsync( piece, rb->host, up_bytes, hipMemcpyHostToDevice, ctx->compute ) );
     if ( aa_status st = ctx->rebase_ring.mark( *rb, ctx->compute ) ) return st;
-    if ( int e = aa::launch_reencode( reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, ctx->reenc_slots, ctx->compute ) )
-      return hip_fail( static_cast<hipError_t>( e ), "k_reencode_inter" );
+    if ( aa_status st = reencode_launch_decision<Call>( ctx, reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, keys ) ) return st;
     HIP_TRY( hipEventRecord( ev[1], ctx->compute ) );
     HIP_TRY( hipMemcpyAsync( staging, piece + up_bytes, result_bytes, hipMemcpyDeviceToHost, ctx->compute ) );
     HIP_TRY( hipEventRecord( ev[2], ctx->compute ) );
@@ -162,15 +217,15 @@ aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
       for ( ;; ) {
         const int k = next.fetch_add( 1 );
         if ( k >= count ) return;
-        aa_reencode_job & j = jobs[first + k];
+        aa_reencode_job & j = jobs[at_job[k]];
         const size_t nmb = size_t( j.hdr->mb_width ) * j.hdr->mb_height;
         const uint8_t * at = staging + result_off[k];
         const uint32_t * masks = reinterpret_cast<const uint32_t *>( at ); at += align_up( nmb * sizeof( uint32_t ) );
         const aa_mb_info * recs = reinterpret_cast<const aa_mb_info *>( at ); at += align_up( nmb * sizeof( aa_mb_info ) );
         const int16_t * dense = reinterpret_cast<const int16_t *>( at );
         const RebaseCounts need = reencode_records( recs, masks, dense, nmb, lf_params[k], nullptr, nullptr );
-        j.num_coeff_blocks = need.blocks; intra_mbs[first + k] = need.intra;
-        if ( need.blocks > j.coeff_capacity_blocks ) { int none = -1; short_job.compare_exchange_strong( none, first + k ); continue; }
+        j.num_coeff_blocks = need.blocks; intra_mbs[at_job[k]] = need.intra;
+        if ( need.blocks > j.coeff_capacity_blocks ) { int none = -1; short_job.compare_exchange_strong( none, at_job[k] ); continue; }
         reencode_records( recs, masks, dense, nmb, lf_params[k], j.mbs_out, j.coeffs_out );
       }
     };
@@ -203,7 +258,7 @@ aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
         aa_reencode_job & j = jobs[i];
         if ( !j.append ) continue;
         aa_frame_header h = *j.hdr;
-        h.key_frame = 0; h.num_coeff_blocks = j.num_coeff_blocks;
+        h.key_frame = Call::kForward && j.hdr->key_frame ? 1 : 0; h.num_coeff_blocks = j.num_coeff_blocks;
         h.num_intra_mbs = intra_mbs[i]; h.has_intra_mb = intra_mbs[i] != 0;
         status[i] = aa_stream_append_records( j.stream, &h, j.mbs_out, j.coeffs_out, &j.frame_index );
         if ( status[i] != AA_OK ) message[i] = g_last_error;
@@ -220,7 +275,7 @@ aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
   }
   const double t_end = now_ms();
   const double timing[5] = { t_end - t_call, ms_kernels, ms_download, ms_records, t_end - t_append };
-  std::memcpy( ctx->reencode_timing, timing, sizeof timing );
+  std::memcpy( Call::timing( ctx ), timing, sizeof timing );
   return AA_OK;
 }
 
@@ -231,13 +286,15 @@ aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
  * input records of a rebase: the block count and the piece's size, the intra count, the intra diagonals.  The appended FrameRec is a
  * device-rebased frame's: no chunk, no batch, rec_block = the piece (job record | macroblock records | intra-row words | dense
  * blocks), dev_job = its start. */
-aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs, int n )
+template <class Call>
+aa_status reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs, int n )
 {
-  if ( !ctx || !jobs || n <= 0 ) return fail( AA_ERR_ARGUMENT, "aa_reencode_device_batch: bad argument" );
+  const std::string who = Call::kDevice;
+  if ( !ctx || !jobs || n <= 0 ) return fail( AA_ERR_ARGUMENT, who + ": bad argument" );
   if ( aa_status st = set_device( ctx ) ) return st;
   // ---- 1. the arguments: nothing is launched, nothing appended unless every job of the call is good ----
   for ( int i = 0; i < n; i++ ) {
-    if ( aa_status st = reencode_check_job( "aa_reencode_device_batch", ctx, jobs, i ) ) return st;
+    if ( aa_status st = reencode_check_job<Call>( Call::kDevice, ctx, jobs, i ) ) return st;
     jobs[i].num_coeff_blocks = 0; jobs[i].num_intra_mbs = 0; jobs[i].frame_index = -1;
   }
 
@@ -256,7 +313,7 @@ aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs,
   const size_t job_bytes = align_up( sizeof( aa_dev_frame ) );
   for ( int first = 0; first < n; ) {
     int count = 0;
-    size_t dense_total = 0, masks_total = 0, records_total = 0, side_total = 0, raster_total = 0, rows_total = 0;
+    size_t dense_total = 0, masks_total = 0, records_total = 0, side_total = 0, raster_total = 0, rows_total = 0, costs_total = 0;
     uint32_t max_mbs = 0;
     while ( first + count < n ) {
       const aa_stream * s = jobs[first + count].stream;
@@ -265,16 +322,18 @@ aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs,
       dense_total += align_up( nmb * AA_REBASE_MB_BYTES ); masks_total += align_up( nmb * sizeof( uint32_t ) );
       records_total += align_up( nmb * sizeof( aa_mb_info ) ); side_total += align_up( nmb * sizeof( aa::ReencNeighbour ) );
       rows_total += align_up( size_t( aa::compact::row_words( s->parser.mb_width(), s->parser.mb_height() ) ) * sizeof( unsigned long long ) );
-      raster_total += s->slot_bytes;
+      raster_total += s->slot_bytes; costs_total += reencode_costs_bytes<Call>( jobs[first + count] );
       max_mbs = std::max<uint32_t>( max_mbs, static_cast<uint32_t>( nmb ) );
       count++;
     }
+    std::vector<int> at_job;                     // table entry -> job of the call
+    const int keys = reencode_slice_order<Call>( jobs, first, count, at_job );
     // the slice's piece: job table | rate models (one upload) | compaction table | filter-level parameters (a second one, once the
     // pieces are known) | partial sums | intra-row words (one download) | masks | records | dense slots | side records | reconstruction
     // rasters.  Pinned: a JobRing entry for each upload; the download lands behind the first one's table.
     const uint32_t stride = aa::compact::runs_of( max_mbs );
-    const size_t table_bytes = align_up( size_t( count ) * sizeof( aa_reencode_dev_job ) ), costs_bytes = align_up( sizeof( aa::ReencCosts ) );
-    const size_t up_bytes = table_bytes + size_t( count ) * costs_bytes;
+    const size_t table_bytes = align_up( size_t( count ) * sizeof( aa_reencode_dev_job ) );
+    const size_t up_bytes = table_bytes + costs_total;
     const size_t ctable_bytes = align_up( size_t( count ) * sizeof( aa_rebase_compact_job ) );
     const size_t up2_bytes = ctable_bytes + align_up( size_t( count ) * sizeof( aa::HeaderParams ) );
     const size_t partial_bytes = align_up( size_t( count ) * stride * sizeof( uint32_t ) );
@@ -298,7 +357,7 @@ aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs,
     std::vector<size_t> rows_at( count );      // a job's intra-row words, from the download's start
     size_t up_off = table_bytes, rows_off = partial_bytes, res_off = 0, side_off = up_bytes + up2_bytes + down_bytes + result_bytes;
     for ( int k = 0; k < count; k++ ) {
-      const aa_reencode_device_job & j = jobs[first + k];
+      const aa_reencode_device_job & j = jobs[at_job[k]];
       aa_stream * s = j.stream;
       const size_t nmb = size_t( s->parser.mb_width() ) * s->parser.mb_height();
       ReencodePlaces at;
@@ -308,8 +367,8 @@ aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs,
       at.dense = results + res_off; res_off += align_up( nmb * AA_REBASE_MB_BYTES );
       at.side = piece + side_off; side_off += align_up( nmb * sizeof( aa::ReencNeighbour ) );
       at.raster = piece + side_off; side_off += s->slot_bytes;
-      reencode_fill_job( table[k], *reinterpret_cast<aa::ReencCosts *>( rb->host + up_off ), lf_params[k], j, at );
-      up_off += costs_bytes;
+      reencode_fill_job<Call>( table[k], rb->host + up_off, lf_params[k], j, at );
+      up_off += reencode_costs_bytes<Call>( j );
       const uint32_t words = aa::compact::row_words( j.hdr->mb_width, j.hdr->mb_height );
       table[k].intra_rows = reinterpret_cast<unsigned long long *>( down_dev + rows_off );
       rows_at[k] = rows_off;
@@ -321,11 +380,10 @@ aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs,
     }
     hipEvent_t ev[5] = { get_event( ctx ), get_event( ctx ), get_event( ctx ), get_event( ctx ), get_event( ctx ) };
     events.insert( events.end(), ev, ev + 5 );
-    if ( !ev[0] || !ev[1] || !ev[2] || !ev[3] || !ev[4] ) return fail( AA_ERR_HIP, "aa_reencode_device_batch: hipEventCreate failed" );
+    if ( !ev[0] || !ev[1] || !ev[2] || !ev[3] || !ev[4] ) return fail( AA_ERR_HIP, who + ": hipEventCreate failed" );
     HIP_TRY( hipEventRecord( ev[0], ctx->compute ) );
     HIP_TRY( hipMemcpyAsync( piece, rb->host, up_bytes, hipMemcpyHostToDevice, ctx->compute ) );
-    if ( int e = aa::launch_reencode( reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, ctx->reenc_slots, ctx->compute ) )
-      return hip_fail( static_cast<hipError_t>( e ), "k_reencode_inter" );
+    if ( aa_status st = reencode_launch_decision<Call>( ctx, reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, keys ) ) return st;
     if ( int e = aa::launch_reencode_count( reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, max_mbs, partials_dev, stride, ctx->compute ) )
       return hip_fail( static_cast<hipError_t>( e ), "k_reencode_count" );
     HIP_TRY( hipEventRecord( ev[1], ctx->compute ) );
@@ -339,14 +397,14 @@ aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs,
 
     // every frame's block count and intra macroblocks, its piece at that size, and where the second kernel puts what
     for ( int k = 0; k < count; k++ ) {
-      aa_reencode_device_job & j = jobs[first + k];
-      Made & m = made[first + k];
+      aa_reencode_device_job & j = jobs[at_job[k]];
+      Made & m = made[at_job[k]];
       const uint32_t mbw = j.hdr->mb_width, mbh = j.hdr->mb_height;
       const size_t nmb = size_t( mbw ) * mbh;
       aa_rebase_compact_job & o = ctable[k];
       uint32_t blocks = 0;
       for ( uint32_t r = 0; r < aa::compact::runs_of( static_cast<uint32_t>( nmb ) ); r++ ) blocks += partials[size_t( k ) * stride + r];
-      if ( blocks > nmb * 25 ) return fail( AA_ERR_HIP, "aa_reencode_device_batch: job " + std::to_string( first + k ) + ": k_reencode_count reports more blocks than the frame can hold" );
+      if ( blocks > nmb * 25 ) return fail( AA_ERR_HIP, who + ": job " + std::to_string( at_job[k] ) + ": k_reencode_count reports more blocks than the frame can hold" );
       const unsigned long long * rows = reinterpret_cast<const unsigned long long *>( down + rows_at[k] );
       FrameRec & rec = m.rec;
       rec.intra_diagonals.assign( mbw + 2 * ( mbh - 1 ), 0 );
@@ -358,7 +416,7 @@ aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs,
       m.bytes = rebase_piece_bytes( job_bytes + mb_bytes + rows_bytes + align_up( size_t( blocks ) * 32 ) );
       if ( aa_status st = dev_alloc( ctx, m.bytes, &m.piece ) ) return st;
       rec.hdr = *j.hdr;
-      rec.hdr.key_frame = 0; rec.hdr.num_coeff_blocks = blocks;
+      rec.hdr.key_frame = Call::kForward && j.hdr->key_frame ? 1 : 0; rec.hdr.num_coeff_blocks = blocks;
       rec.hdr.num_intra_mbs = j.num_intra_mbs; rec.hdr.has_intra_mb = j.num_intra_mbs != 0;
       rec.rec_block = m.piece; rec.rec_bytes = m.bytes;
       rec.dev_job = reinterpret_cast<const aa_dev_frame *>( m.piece );
@@ -400,9 +458,16 @@ aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs,
   give_back.keep = true;
   const double t_end = now_ms();
   const double timing[5] = { t_end - t_call, ms_kernels, ms_download, 0.0, t_end - t_append };
-  std::memcpy( ctx->reencode_timing, timing, sizeof timing );
+  std::memcpy( Call::timing( ctx ), timing, sizeof timing );
   return AA_OK;
 }
+
+} // namespace
+
+extern "C" {
+
+aa_status aa_reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n ) { return reencode_batch<ReencodeCall>( ctx, jobs, n ); }
+aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs, int n ) { return reencode_device_batch<ReencodeCall>( ctx, jobs, n ); }
 
 aa_status aa_reencode_last_timing( aa_ctx * ctx, double out[5] )
 {

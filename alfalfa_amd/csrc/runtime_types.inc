@@ -229,8 +229,9 @@ struct aa_ctx {
   JobRing rgb_ring, quality_ring;
   double rebase_timing[5] = {};             // aa_rebase_last_timing
   double reencode_timing[5] = {};           // aa_reencode_last_timing
+  double encode_timing[5] = {};             // aa_encode_last_timing
   double serialize_timing[5] = {};          // aa_serialize_last_timing
-  int reenc_slots = 16;                     // macroblocks of an anti-diagonal per round of k_reencode_inter (aa_ctx_set_reencode_slots)
+  int reenc_slots = 16;                     // macroblocks of an anti-diagonal per round of k_reencode_inter, k_encode_key and k_encode_inter (aa_ctx_set_reencode_slots)
   int lf_round = 4;                         // aa_lf_search_decode_batch: levels per job and round; lf_jobs_per_slice: jobs per slice, 0 = by memory (aa_ctx_set_lf_search_round)
   int lf_jobs_per_slice = 0;
   double lf_timing[8] = {};                 // aa_lf_search_last_timing

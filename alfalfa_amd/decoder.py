@@ -494,20 +494,37 @@ class Context:
         records=False (aa_reencode_device_batch): the new frame's records are compacted on the device and stay there, as with
         rebase( records=False ) -- the result per job is (frame_index, num_coeff_blocks).  Such a frame is always appended: together
         with append=False this raises ValueError."""
+        return self._decide_frames("reencode_as_inter", self.L.aa_reencode_batch, self.L.aa_reencode_device_batch, decoders, headers, targets, quality, append, records)
+
+    def encode_frames(self, decoders, headers, targets, quality="best", append=True, records=True):
+        """The forward encoder (aa_encode_batch; Encoder::encode_with_quantizer, encoder.cc:559-575: xc-enc -i y4m -y QI -q best|rt), one
+        new frame per decoder: targets[i] encoded as a key frame where headers[i]["key_frame"] is set (encode_raster<KeyFrame>; needs
+        no reference and no earlier frame) and otherwise as an inter frame predicted from decoders[i]'s current last reference
+        (encode_raster<InterFrame>), every macroblock's mode, vector and coefficients as the reference's single-pass encoder chooses
+        them (quality: "best" or "rt", for all jobs or one per job).  One call may mix kinds, sizes and qualities.  headers[i] -- the
+        caller's: q_index and quant (aa.quant_factors), loop filter fields, refresh flags -- and targets[i] as for rebase.  -> per job
+        (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]) as reencode_as_inter returns them; with append False nothing is appended
+        and frame_index is -1.  The frames go on to lf_search_decode / decode_batch and serialize_frames( optimise=True ).  Synchronous.
+        records=False (aa_encode_device_batch): the new frame's records are compacted on the device and stay there -- the result per
+        job is (frame_index, num_coeff_blocks).  Such a frame is always appended: together with append=False this raises ValueError."""
+        return self._decide_frames("encode_frames", self.L.aa_encode_batch, self.L.aa_encode_device_batch, decoders, headers, targets, quality, append, records)
+
+    def _decide_frames(self, who, host_call, device_call, decoders, headers, targets, quality, append, records):
+        """reencode_as_inter and encode_frames: the same jobs into two pairs of ABI calls."""
         import torch
         n = len(decoders)
         if n == 0 or len(headers) != n or len(targets) != n:
-            raise ValueError("reencode_as_inter: need as many headers and targets as decoders, and at least one")
+            raise ValueError(who + ": need as many headers and targets as decoders, and at least one")
         qualities = [quality] * n if isinstance(quality, str) else list(quality)
         if len(qualities) != n or any(q not in ("best", "rt") for q in qualities):
-            raise ValueError("reencode_as_inter: quality is \"best\" or \"rt\", one for all jobs or one per job")
+            raise ValueError(who + ": quality is \"best\" or \"rt\", one for all jobs or one per job")
         if not records:
             if not append:
-                raise ValueError("reencode_as_inter: records=False keeps the frame on the device, where it is always appended; append=False needs records=True")
+                raise ValueError(who + ": records=False keeps the frame on the device, where it is always appended; append=False needs records=True")
             jobs = (capi.ReencodeDeviceJob * n)()
             keep = []
             for i, (d, header, t) in enumerate(zip(decoders, headers, targets)):
-                t = self._target_planes("reencode_as_inter", i, d, t)
+                t = self._target_planes(who, i, d, t)
                 hdr = self._header_struct(header)
                 j = jobs[i]
                 j.stream, j.hdr, j.quality = d.h, C.pointer(hdr), (1 if qualities[i] == "rt" else 0)
@@ -515,12 +532,12 @@ class Context:
                 j.target.y_stride, j.target.uv_stride = t[0].stride(0), t[1].stride(0)
                 keep.append((hdr, t))
             torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
-            capi.check(self.L.aa_reencode_device_batch(self.h, jobs, n))
+            capi.check(device_call(self.h, jobs, n))
             return [(jobs[i].frame_index, jobs[i].num_coeff_blocks) for i in range(n)]
         jobs = (capi.ReencodeJob * n)()
         keep, outs = [], []
         for i, (d, header, t) in enumerate(zip(decoders, headers, targets)):
-            t = self._target_planes("reencode_as_inter", i, d, t)
+            t = self._target_planes(who, i, d, t)
             hdr = self._header_struct(header)
             nmb = hdr.mb_width * hdr.mb_height
             mb_out = np.zeros(nmb, dtype=MB_INFO_DTYPE)
@@ -534,7 +551,7 @@ class Context:
             keep.append((hdr, t))
             outs.append((mb_out, cf, hdr.mb_width, hdr.mb_height))
         torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()      # (the targets are ready; the call itself waits for its kernel)
-        capi.check(self.L.aa_reencode_batch(self.h, jobs, n))
+        capi.check(host_call(self.h, jobs, n))
         return [(jobs[i].frame_index, mb_out.reshape(mbh, mbw), cf[:jobs[i].num_coeff_blocks].copy()) for i, (mb_out, cf, mbw, mbh) in enumerate(outs)]
 
     def serialize_frames(self, decoders, frame_indices, headers, exts, probs_before=None, advance_state=False, capacity=None, optimise=False, sub_modes=None, details=False):
@@ -601,8 +618,15 @@ class Context:
         capi.check(self.L.aa_reencode_last_timing(self.h, out))
         return dict(zip(("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms"), out))
 
+    def encode_timing(self):
+        """The last encode_frames of this context (aa_encode_last_timing), ms: as reencode_timing."""
+        out = (C.c_double * 5)()
+        capi.check(self.L.aa_encode_last_timing(self.h, out))
+        return dict(zip(("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms"), out))
+
     def set_reencode_slots(self, slots):
-        """Macroblocks of an anti-diagonal per round of the re-encode kernel (aa_ctx_set_reencode_slots: 1..16, default 16)."""
+        """Macroblocks of an anti-diagonal per round of the re-encode kernel and of the forward encoder's two (aa_ctx_set_reencode_slots:
+        1..16, default 16)."""
         capi.check(self.L.aa_ctx_set_reencode_slots(self.h, int(slots)))
 
     LF_MEASURES = {"ssim": capi.AA_LF_MEASURE_SSIM, "sse": capi.AA_LF_MEASURE_SSE}
@@ -784,6 +808,11 @@ class Decoder:
         """One new frame of this decoder by re-encode (Context.reencode_as_inter) -> (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]), or
         with records=False (frame_index, num_coeff_blocks)."""
         return self.ctx.reencode_as_inter([self], [header], [target], quality, append, records)[0]
+
+    def encode_frame(self, header, target, quality="best", append=True, records=True):
+        """One new frame of this decoder by the forward encoder (Context.encode_frames), a key frame where header["key_frame"] is set ->
+        (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]), or with records=False (frame_index, num_coeff_blocks)."""
+        return self.ctx.encode_frames([self], [header], [target], quality, append, records)[0]
 
     def serialize_frame(self, frame_index, header, ext, probs_before=None, advance_state=False, capacity=None, sub_modes=None, optimise=False, details=False):
         """One frame of this decoder, held as records, as VP8 bytes (Context.serialize_frames)."""

@@ -597,9 +597,35 @@ aa_status aa_reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs,
 /* As aa_rebase_last_timing, for the last successful aa_reencode_batch (or aa_reencode_device_batch, see there): [1] job table and rate
  * models up and the kernel. */
 aa_status aa_reencode_last_timing( aa_ctx * ctx, double out[5] );
-/* How many macroblocks of an anti-diagonal a round of the re-encode kernel takes (1..16, default 16; also ALFALFA_AMD_REENC_SLOTS at
+/* How many macroblocks of an anti-diagonal a round of the re-encode kernel (and of the two kernels of the forward encoder) takes (1..16, default 16; also ALFALFA_AMD_REENC_SLOTS at
  * context creation): with a small cap the several-rounds-per-diagonal path runs on a small frame (tests). */
 aa_status aa_ctx_set_reencode_slots( aa_ctx * ctx, int slots );
+
+/* The FORWARD ENCODER (Encoder::encode_with_quantizer, encoder.cc:559-575: what xc-enc -i y4m -y QI -q best|rt does to every picture):
+ * a raster in device memory becomes a new frame with the modes, vectors and coefficients the reference's single-pass encoder chooses --
+ * a KEY frame (hdr->key_frame set; encode_raster<KeyFrame>, encode_intra.cc:388-456) or an INTER frame predicted from the stream's
+ * current last reference (encode_raster<InterFrame>, encode_inter.cc:577-653).  One call may mix kinds, sizes and qualities; each kind is
+ * one kernel over its jobs, a workgroup per job, on the re-encode's schedule (aa_ctx_set_reencode_slots caps its rounds too).
+ * The jobs are aa_reencode_job / aa_reencode_device_job and mean what they mean there -- stream, header of the new frame (quant[0][*],
+ * q_index, loop filter fields, refresh flags: the caller's; the probabilities are aa_serialize_batch's, optimise set), target planes on the
+ * device, quality, append, the records out -- and the results are taken by aa_lf_search_decode_batch, aa_decode_batch and
+ * aa_serialize_batch like a re-encoded frame's.  What differs from the re-encode:
+ *   - the rate and distortion multipliers are update_rd_multipliers' (encoder.cc:178-193) of the job's quantiser, not 300 / 1;
+ *   - a key frame weighs its 16x16 modes with the key frame's mode costs, tries B_PRED under both qualities, has no inter candidate and
+ *     reads no reference: a key job needs no decoded frame, no reference and no prior state, and once it is appended and decoded all
+ *     three references are the new frame (its lf_level is hdr's level, unadjusted: a key frame resets the stream's adjustments);
+ *   - an inter frame's diamond search adds the rate of a site's vector to its SAD (sad_motion_vector_cost, costs.cc:231-240).
+ * First pass only: plain division, no trellis.  Errors as aa_reencode_batch's (messages begin "aa_encode_batch: job i:" /
+ * "aa_encode_device_batch: job i:"; nothing is appended to any stream of a refused call): null pointers; a quality that is none;
+ * segmentation_enabled (AA_ERR_UNSUPPORTED, as the reference); a header of another size; a stream listed twice; an INTER job on a stream
+ * whose last reference is no decoded frame (AA_ERR_LOGIC) or that holds a frame appended but not decoded (AA_ERR_LOGIC);
+ * coeff_capacity_blocks too small.  (Still AA_ABI_VERSION 4: an addition.) */
+typedef aa_reencode_job aa_encode_job;
+typedef aa_reencode_device_job aa_encode_device_job;
+aa_status aa_encode_batch( aa_ctx * ctx, aa_encode_job * jobs, int n );
+aa_status aa_encode_device_batch( aa_ctx * ctx, aa_encode_device_job * jobs, int n );
+/* As aa_reencode_last_timing, for the last successful aa_encode_batch or aa_encode_device_batch. */
+aa_status aa_encode_last_timing( aa_ctx * ctx, double out[5] );
 
 /* THE LOOP-FILTER LEVEL OF APPENDED FRAMES, searched for a whole batch (the last statement of Encoder::reencode_as_interframe,
  * reencode.cc:126: apply_best_loopfilter_settings, encoder.cc:459-516) -- and the DECODE of those frames.  Job i's frame is its stream's
