@@ -12,4 +12,4 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 from .decoder import AlfalfaError, Context, Decoder, FilePlayer, Parser, Quality, psnr, read_ivf, serialize_host, with_zero_lf_deltas  # noqa: F401
-from .capi import quant_factors  # noqa: F401
+from .capi import estimate_carry, quant_factors, target_size_range  # noqa: F401

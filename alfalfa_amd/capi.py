@@ -143,6 +143,19 @@ class ReencodeDeviceJob(C.Structure):
 
 EncodeJob, EncodeDeviceJob = ReencodeJob, ReencodeDeviceJob       # aa_encode_job / aa_encode_device_job are typedefs of them
 
+
+
+class EstimateSizeJob(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("target", QualityRef), ("key_frame", C.c_int), ("quality", C.c_int), ("q_index", C.c_int), ("carry", C.c_uint8 * 4),
+                ("size_out", C.c_uint64)]
+
+
+class TargetSizeJob(C.Structure):
+    _fields_ = [("stream", C.c_void_p), ("target", QualityRef), ("key_frame", C.c_int), ("quality", C.c_int), ("q_lo", C.c_int), ("q_hi", C.c_int),
+                ("target_size", C.c_uint64), ("carry", C.c_uint8 * 4), ("q_index", C.c_int), ("estimates", C.c_int), ("visited_q", C.c_int * 8),
+                ("visited_size", C.c_uint64 * 8)]
+
+
 AA_LF_MEASURE_SSIM, AA_LF_MEASURE_SSE = 0, 1
 
 
@@ -216,6 +229,9 @@ SYMBOLS = [
     ("aa_encode_batch", C.c_int, [_P, C.POINTER(ReencodeJob), C.c_int]),
     ("aa_encode_device_batch", C.c_int, [_P, C.POINTER(ReencodeDeviceJob), C.c_int]),
     ("aa_encode_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("aa_estimate_size_batch", C.c_int, [_P, C.POINTER(EstimateSizeJob), C.c_int]), ("aa_target_size_batch", C.c_int, [_P, C.POINTER(TargetSizeJob), C.c_int]),
+    ("aa_target_size_range", None, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]), ("aa_ctx_set_target_size_round", C.c_int, [_P, C.c_int]),
+    ("aa_target_size_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_lf_search_decode_batch", C.c_int, [_P, C.POINTER(LfSearchJob), C.c_int, C.c_int]),
     ("aa_ctx_set_lf_search_round", C.c_int, [_P, C.c_int, C.c_int]), ("aa_lf_search_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_parser_last_header_ext", C.c_int, [_P, C.POINTER(FrameHeaderExt)]), ("aa_stream_last_header_ext", C.c_int, [_P, C.POINTER(FrameHeaderExt)]),
@@ -294,6 +310,22 @@ def quant_factors(qi, deltas=None):
         d = (C.c_int8 * 5)(*deltas)
     lib().aa_quant_factors(int(qi), d, out)
     return list(out)
+
+
+def target_size_range(last_q=None):
+    """The range Encoder::encode_with_target_size searches (encoder.cc:597-608) -> (q_lo, q_hi): (4, 127), or around the quantiser index
+    of the encoder's last frame -- last_q - 16 where that is not below 4, last_q + 16 capped at 127.  The reference keeps a last index
+    under real-time quality only: pass last_q there and nowhere else (aa_target_size_range)."""
+    lo, hi = C.c_int(), C.c_int()
+    lib().aa_target_size_range(-1 if last_q is None else int(last_q), C.byref(lo), C.byref(hi))
+    return lo.value, hi.value
+
+
+def estimate_carry():
+    """The carry a stream's first inter estimate starts from (Context.estimate_frame_sizes, Context.target_size_q): the three reference
+    probabilities of a default-constructed header, all zero, and vector cost tables that are not filled yet.  Byte 3 becomes 1 once the
+    stream's first inter frame has been ENCODED; bytes 0..2 are handed on from every inter estimate to the next."""
+    return (0, 0, 0, 0)
 
 
 def raster_geometry(width, height):

@@ -105,6 +105,13 @@ struct aa_reencode_dev_job {
   unsigned long long * intra_rows;   // aa_reencode_device_batch: where k_reencode_count leaves the frame's intra-row words (else null, unused)
 };
 
+// One job of a size estimate (aa_estimate_size_batch, a round of aa_target_size_batch), beside its aa_reencode_dev_job over the SMALL frame:
+// the tables the small frame's tokens are coded with and where k_estimate_tokens leaves its three words
+struct aa_estimate_dev_job {
+  const uint8_t * token_probs; // [4][8][3][11]: the stream's tables before the frame; a key estimate: the defaults
+  uint32_t * result;           // [4]: the DCT partition's bytes, macroblocks with coefficients, intra macroblocks, 0
+};
+
 // One (stream, frame) of a serialisation (aa_serialize_batch): the frame's records as reconstruction reads them, the tables its tokens are
 // coded with, and where the DCT partitions go: partition p owns [out + p * region, out + (p + 1) * region) and reports the bytes it takes
 // -- more than `region`: it did not fit, and what did not fit was not stored -- in sizes[p].
@@ -255,6 +262,11 @@ int launch_reencode( const aa_reencode_dev_job * jobs, int n, int slots, void * 
 // encode_kernels.hip: the same over jobs of ONE kind of the forward encoder -- key: k_encode_key (costs = EncKeyCosts, no reference read),
 // otherwise k_encode_inter (costs = EncInterCosts)
 int launch_encode( const aa_reencode_dev_job * jobs, int n, bool key, int slots, void * stream );
+// estimate_kernels.hip: the same over jobs of ONE kind of the size estimate, whose frames are the small ones -- key: k_estimate_key (costs =
+// EstKeyCosts), otherwise k_estimate_inter (costs = EstInterCosts) -- and, behind them on the same stream, k_estimate_tokens: a lane per job,
+// lanes_per_wave (1..64) to a wave, sizes[i] beside jobs[i]
+int launch_estimate( const aa_reencode_dev_job * jobs, int n, bool key, int slots, void * stream );
+int launch_estimate_tokens( const aa_reencode_dev_job * jobs, const aa_estimate_dev_job * sizes, int n, int lanes_per_wave, void * stream );
 // reencode_compact_kernels.hip, behind launch_reencode on the same stream: the pair of launch_rebase_count / launch_rebase_compact over the
 // records the decision wrote.  k_reencode_count also leaves every frame's intra-row words in jobs[i].intra_rows; k_reencode_compact copies
 // them from there (outs[i].rows) and sets lf_level by lf[i] (aa::HeaderParams, n of them)

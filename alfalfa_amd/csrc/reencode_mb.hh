@@ -44,6 +44,18 @@ struct ReencMb {
       row( static_cast<int>( m / j.base.mbw ) ), pw( j.base.mbw * 16 ), ph( j.base.mbh * 16 ), cw( j.base.mbw * 8 ), ch( j.base.mbh * 8 ), x0( col * 16 ), y0( row * 16 )
   {}
 
+  // Where the macroblock's original, its search and its candidates' predictions lie, and how large the reference planes are.  A frame
+  // encoded whole: where the macroblock itself lies, in planes of the frame's size.  The size estimate (P::kSampled; Encoder::estimate_size,
+  // size_estimation.cc): the job's frame is the small one, macroblock (col, row) of it stands for the original's (4 col, 4 row) -- the
+  // original is read there and the candidates predict from there (reference.macroblock( original_mb.Y.column(), .. ), encode_inter.cc:184,
+  // 254,448) -- while the census, the clamp, the intra neighbours and the reconstruction are the small frame's at (col, row).
+  AA_MHD int tx() const { if constexpr ( P::kSampled ) return x0 * 4; else return x0; }
+  AA_MHD int ty() const { if constexpr ( P::kSampled ) return y0 * 4; else return y0; }
+  AA_MHD int tcx() const { if constexpr ( P::kSampled ) return col * 32; else return col * 8; }      // (the same in the chroma planes)
+  AA_MHD int tcy() const { if constexpr ( P::kSampled ) return row * 32; else return row * 8; }
+  AA_MHD int rw() const { if constexpr ( P::kSampled ) return P::full_mbw( C ) * 16; else return pw; }
+  AA_MHD int rh() const { if constexpr ( P::kSampled ) return P::full_mbh( C ) * 16; else return ph; }
+
   // a neighbour's side record: written by another wave of the workgroup in an earlier round, read past the CU's L1
   AA_MHD ReencNeighbour neighbour( const size_t at ) const
   {
@@ -53,12 +65,21 @@ struct ReencMb {
     return n;
   }
 
+  // The four pixels above and to the right of the macroblock (the above-right predictor of its fourth sub-block column): beyond the
+  // raster's last column the pixel to their left is replicated.  The estimate's reconstruction raster is the ORIGINAL's size with only
+  // the small frame's corner written (size_estimation.cc:56,119): beyond the small frame's last column, but inside the raster, lie pixels
+  // no estimate writes -- zero in a raster fresh from the allocator, and zero here.
+  AA_MHD bool above_right_beyond_raster() const { if constexpr ( P::kSampled ) return col + 1 >= P::full_mbw( C ); else return x0 + 16 >= pw; }
+  AA_MHD bool above_right_unwritten() const { if constexpr ( P::kSampled ) return x0 + 16 >= pw; else return false; }
+  // (what they hold is the policy's to say: 0 under the product's two, reencode_search.hh)
+  AA_MHD uint32_t unwritten_pixels() const { if constexpr ( P::kSampled ) return P::unwritten_pixels( C, row ); else return 0; }
+
   // the lane's target block, and the slot's picture of the neighbourhood (the layout of k_rebase_intra, staged by sixteen lanes)
   AA_MHD void stage()
   {
     const uint8_t * Y = J.recon[0];
     lanes.each( [&]( const int b, ReencRegs & R ) {
-      const uint8_t * t = J.target[0] + static_cast<int64_t>( y0 + ( b >> 2 ) * 4 ) * J.target_stride[0] + x0 + ( b & 3 ) * 4;
+      const uint8_t * t = J.target[0] + static_cast<int64_t>( ty() + ( b >> 2 ) * 4 ) * J.target_stride[0] + tx() + ( b & 3 ) * 4;
 #if defined( __HIP_DEVICE_COMPILE__ )
 #pragma unroll
 #endif
@@ -68,7 +89,8 @@ struct ReencMb {
         if ( y0 == 0 ) v = 0x7F7F7F7Fu;
         else if ( b == 0 ) v = x0 > 0 ? load_recon_u32( Y + static_cast<size_t>( y0 - 1 ) * pw + x0 - 4 ) : 0x81818181u;
         else if ( b <= 4 ) v = load_recon_u32( Y + static_cast<size_t>( y0 - 1 ) * pw + x0 + ( b - 1 ) * 4 );
-        else if ( x0 + 16 >= pw ) v = 0x01010101u * ( load_recon_u32( Y + static_cast<size_t>( y0 - 1 ) * pw + pw - 4 ) >> 24 );   // replicate: prediction.cc:144-151
+        else if ( above_right_beyond_raster() ) v = 0x01010101u * ( load_recon_u32( Y + static_cast<size_t>( y0 - 1 ) * pw + pw - 4 ) >> 24 );   // replicate: prediction.cc:144-151
+        else if ( above_right_unwritten() ) v = unwritten_pixels();
         else v = load_recon_u32( Y + static_cast<size_t>( y0 - 1 ) * pw + x0 + 16 );
         *reinterpret_cast<uint32_t *>( &S.L.y[0][b * 4] ) = v;
       } else if ( b < 12 ) {
@@ -117,7 +139,13 @@ struct ReencMb {
   }
   AA_MHD void predict_inter( const int b, const int mvx, const int mvy, int ( &p )[16] ) const
   {
-    predict_unit( J.ref[1][0], pw, ph, x0 + ( b & 3 ) * 4, y0 + ( b >> 2 ) * 4, mvx, mvy, p );
+    predict_unit( J.ref[1][0], rw(), rh(), tx() + ( b & 3 ) * 4, ty() + ( b >> 2 ) * 4, mvx, mvy, p );
+  }
+  // the estimate's reconstruction of an inter macroblock predicts again, at the SMALL frame's position of the same reference
+  // (reconstruct_inter: raster.Y.inter_predict, macroblock.cc:589-591): that is what later intra neighbours see
+  AA_MHD void predict_inter_small( const int b, const int mvx, const int mvy, int ( &p )[16] ) const
+  {
+    predict_unit( J.ref[1][0], rw(), rh(), x0 + ( b & 3 ) * 4, y0 + ( b >> 2 ) * 4, mvx, mvy, p );
   }
 
   // ---- what reencode_search.hh asks (variance.cc:32-82, the C++ branch) ----
@@ -167,7 +195,7 @@ struct ReencMb {
     for ( int sb = 0; sb < 16; sb++ ) {
       const int bx = sb & 3, by = sb >> 2;
       const int ar = by * 4, ac = bx * 4 + 3;       // index of (row -1, col -1) of this sub-block in the picture
-      const uint8_t * target = J.target[0] + static_cast<int64_t>( y0 + by * 4 ) * J.target_stride[0] + x0 + bx * 4;
+      const uint8_t * target = J.target[0] + static_cast<int64_t>( ty() + by * 4 ) * J.target_stride[0] + tx() + bx * 4;
       lanes.each( [&]( const int b, ReencRegs & R ) {
         if ( b < 13 ) {
           uint8_t e;
@@ -221,11 +249,12 @@ struct ReencMb {
 
   // ---- the chosen mode applied (encode_intra.cc:169-222, encode_inter.cc:375-435, FIRST_PASS; the statements of k_rebase_*) ----
   // every lane's prediction is in its R.p: 16 luma slots, the Y2 slot, the reconstruction -> mask bits 0..15 and 24
-  AA_MHD uint32_t code_luma_with_y2()
+  // (inter, mv: read by the estimate alone, which reconstructs an inter macroblock from another prediction than it coded)
+  AA_MHD uint32_t code_luma_with_y2( const bool inter, const Mv mv )
   {
     lanes.each( [&]( const int b, ReencRegs & R ) {
       const int bx = ( b & 3 ) * 4, by = ( b >> 2 ) * 4;
-      forward_block( J.target[0] + static_cast<int64_t>( y0 + by ) * J.target_stride[0] + x0 + bx, J.target_stride[0], R.p, R.q );
+      forward_block( J.target[0] + static_cast<int64_t>( ty() + by ) * J.target_stride[0] + tx() + bx, J.target_stride[0], R.p, R.q );
       S.L.dcs[b] = static_cast<int16_t>( R.q[0] );
       R.q[0] = 0;
       R.nz = quantize_block( R.q, J.quant[Q_Y_DC], J.quant[Q_Y_AC] );
@@ -237,6 +266,7 @@ struct ReencMb {
       int q2[16], dc_back;
       R.nz2 = y2_block( S.L.dcs, J.quant, b, q2, dc_back );
       if ( b == 0 ) store_block( J.coeffs + ( mi * 25 + 24 ) * 16, q2 );
+      if constexpr ( P::kSampled ) { if ( inter ) predict_inter_small( b, mv.x, mv.y, R.p ); }
       uint32_t rows[4];
       reconstruct_block( R.q, J.quant[Q_Y_DC], J.quant[Q_Y_AC], true, dc_back, R.p, rows );
       store_rows( J.recon[0] + static_cast<size_t>( y0 + by ) * pw + x0 + bx, pw, rows );
@@ -256,6 +286,21 @@ struct ReencMb {
     } );
     return S.trial_mask;
   }
+  // chroma_block (rebase_inl.hh) for the estimate: the original read at the original's position, the prediction that is coded (p) and the
+  // one the reconstruction is made from (ps: the same but for an inter macroblock), the reconstruction at the small frame's position
+  AA_MHD bool chroma_block_sampled( const int pl, const int cb, const int ( &p )[16], const int ( &ps )[16] )
+  {
+    const int bx = ( cb & 1 ) * 4, by = ( cb >> 1 ) * 4;
+    int q[16];
+    forward_block( J.target[1 + pl] + static_cast<int64_t>( tcy() + by ) * J.target_stride[1] + tcx() + bx, J.target_stride[1], p, q );
+    const bool nz = quantize_block( q, J.quant[Q_UV_DC], J.quant[Q_UV_AC] );
+    store_block( J.coeffs + ( mi * 25 + 16 + pl * 4 + cb ) * 16, q );
+    uint32_t rows[4];
+    reconstruct_block( q, J.quant[Q_UV_DC], J.quant[Q_UV_AC], false, 0, ps, rows );
+    store_rows( J.recon[1 + pl] + static_cast<size_t>( row * 8 + by ) * cw + col * 8 + bx, cw, rows );
+    return nz;
+  }
+
   // chroma of an intra macroblock: uv_mode by distortion alone (pick_uv_mode), then lanes 0..7 one block each -> mask bits 16..23
   AA_MHD uint32_t code_chroma_intra( int & uv_mode )
   {
@@ -269,7 +314,7 @@ struct ReencMb {
         const int pl = b >> 2, cb = b & 3;
         int p[16];
         predict_chroma( m, pl, cb, p );
-        const uint8_t * t = J.target[1 + pl] + static_cast<int64_t>( row * 8 + ( cb >> 1 ) * 4 ) * J.target_stride[1] + col * 8 + ( cb & 1 ) * 4;
+        const uint8_t * t = J.target[1 + pl] + static_cast<int64_t>( tcy() + ( cb >> 1 ) * 4 ) * J.target_stride[1] + tcx() + ( cb & 1 ) * 4;
         uint32_t e = 0;
 #if defined( __HIP_DEVICE_COMPILE__ )
 #pragma unroll
@@ -282,7 +327,8 @@ struct ReencMb {
       if ( b >= 8 ) return 0u;
       int p[16];
       predict_chroma( mode, b >> 2, b & 3, p );
-      return chroma_block( J, mi, col, row, b >> 2, b & 3, p ) ? 1u << ( 16 + b ) : 0u; } );
+      if constexpr ( P::kSampled ) return chroma_block_sampled( b >> 2, b & 3, p, p ) ? 1u << ( 16 + b ) : 0u;
+      else return chroma_block( J, mi, col, row, b >> 2, b & 3, p ) ? 1u << ( 16 + b ) : 0u; } );
   }
   // chroma of an inter macroblock: the rounded average of four equal luma vectors (chroma_mb_inter_predict)
   AA_MHD uint32_t code_chroma_inter( const int mvx, const int mvy )
@@ -292,8 +338,15 @@ struct ReencMb {
       if ( b >= 8 ) return 0u;
       const int pl = b >> 2, cb = b & 3;
       int p[16];
-      predict_unit( J.ref[1][1 + pl], cw, ch, col * 8 + ( cb & 1 ) * 4, row * 8 + ( cb >> 1 ) * 4, cx, cy, p );
-      return chroma_block( J, mi, col, row, pl, cb, p ) ? 1u << ( 16 + b ) : 0u; } );
+      if constexpr ( P::kSampled ) {
+        int ps[16];
+        predict_unit( J.ref[1][1 + pl], rw() / 2, rh() / 2, tcx() + ( cb & 1 ) * 4, tcy() + ( cb >> 1 ) * 4, cx, cy, p );
+        predict_unit( J.ref[1][1 + pl], rw() / 2, rh() / 2, col * 8 + ( cb & 1 ) * 4, row * 8 + ( cb >> 1 ) * 4, cx, cy, ps );
+        return chroma_block_sampled( pl, cb, p, ps ) ? 1u << ( 16 + b ) : 0u;
+      } else {
+        predict_unit( J.ref[1][1 + pl], cw, ch, col * 8 + ( cb & 1 ) * 4, row * 8 + ( cb >> 1 ) * 4, cx, cy, p );
+        return chroma_block( J, mi, col, row, pl, cb, p ) ? 1u << ( 16 + b ) : 0u;
+      } } );
   }
 
   // The macroblock: census, decision, the chosen mode applied, its record and its side record.
@@ -321,7 +374,7 @@ struct ReencMb {
       lanes.each( [&]( const int b, ReencRegs & R ) {
         if constexpr ( P::kKey ) predict16( mode, b, R.p );
         else { if ( inter ) predict_inter( b, choice.mv.x, choice.mv.y, R.p ); else predict16( mode, b, R.p ); } } );
-      mask = code_luma_with_y2();
+      mask = code_luma_with_y2( inter, choice.mv );
     }
     if constexpr ( !P::kKey ) mask |= inter ? code_chroma_inter( choice.mv.x, choice.mv.y ) : code_chroma_intra( uv_mode );
     else mask |= code_chroma_intra( uv_mode );

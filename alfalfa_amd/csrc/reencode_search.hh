@@ -137,7 +137,7 @@ AA_MHD uint32_t sad_motion_vector_cost( const uint16_t * mv_sad, int mvx, int mv
 // aa_reencode_batch: Encoder::reencode_as_interframe.  Constants 300 / 1; a site of the search costs its SAD (see diamond_search).
 struct ReencodePolicy {
   using Costs = ReencCosts;
-  static constexpr bool kKey = false;
+  static constexpr bool kKey = false, kSampled = false;
   AA_MHD static uint32_t rate_mul( const Costs & ) { return kRateMultiplier; }
   AA_MHD static uint32_t dist_mul( const Costs & ) { return kDistortionMultiplier; }
   AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.bmode[above][left]; }
@@ -149,7 +149,7 @@ struct ReencodePolicy {
 // aa_encode_batch, an inter frame: encode_raster<InterFrame>.  The job's multipliers; a site costs its SAD and the rate of its vector.
 struct ForwardInterPolicy {
   using Costs = EncInterCosts;
-  static constexpr bool kKey = false;
+  static constexpr bool kKey = false, kSampled = false;
   AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.rate_mul; }
   AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.dist_mul; }
   AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.base.bmode[above][left]; }
@@ -162,12 +162,49 @@ struct ForwardInterPolicy {
 // exclusion, encode_intra.cc:98-102, is the inter frames' alone).
 struct KeyPolicy {
   using Costs = EncKeyCosts;
-  static constexpr bool kKey = true;
+  static constexpr bool kKey = true, kSampled = false;
   AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.rate_mul; }
   AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.dist_mul; }
   AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.bmode[above][left]; }
   AA_MHD static uint32_t mbmode_intra( const Costs & C, int mode ) { return C.mbmode[mode]; }
   AA_MHD static bool tries_bpred( const Costs & ) { return true; }
+};
+
+// aa_estimate_size_batch / aa_target_size_batch: Encoder::estimate_size (size_estimation.cc) -- the forward encoder's first pass over
+// every fourth macroblock in each direction, as a frame of its own.  The decisions are the forward policies'; kSampled tells the macroblock
+// code (reencode_mb.hh) that the job's frame is the SMALL one: macroblock (c, r) of it encodes the original's macroblock (4c, 4r), searches
+// and predicts its candidates at that position of the full-size reference, and reconstructs at (c, r).  The cost block carries the
+// original's size in macroblocks behind the forward encoder's block.
+struct EstInterCosts { EncInterCosts enc; uint32_t full_mbw, full_mbh; };
+struct EstKeyCosts { EncKeyCosts enc; uint32_t full_mbw, full_mbh; };
+static_assert( sizeof( EstInterCosts ) % 8 == 0 && sizeof( EstKeyCosts ) % 8 == 0, "the estimate's cost blocks sit in a table of 8-byte aligned pieces" );
+struct EstimateInterPolicy {
+  using Costs = EstInterCosts;
+  static constexpr bool kKey = false, kSampled = true;
+  AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.enc.rate_mul; }
+  AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.enc.dist_mul; }
+  AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.enc.base.bmode[above][left]; }
+  AA_MHD static uint32_t mbmode_intra( const Costs & C, int mode ) { return C.enc.base.mbmode_intra[mode]; }
+  AA_MHD static bool tries_bpred( const Costs & C ) { return C.enc.base.quality != REENC_REALTIME; }
+  AA_MHD static const ReencCosts & inter( const Costs & C ) { return C.enc.base; }
+  AA_MHD static uint32_t site_cost( const Costs & C, int mvx, int mvy, uint32_t sad ) { return ForwardInterPolicy::site_cost( C.enc, mvx, mvy, sad ); }
+  AA_MHD static int full_mbw( const Costs & C ) { return static_cast<int>( C.full_mbw ); }
+  AA_MHD static int full_mbh( const Costs & C ) { return static_cast<int>( C.full_mbh ); }
+  // the four pixels above-right of a macroblock of the small frame's last column, row >= 1, which no estimate writes (reencode_mb.hh): zero
+  AA_MHD static uint32_t unwritten_pixels( const Costs &, int ) { return 0; }
+};
+struct EstimateKeyPolicy {
+  using Costs = EstKeyCosts;
+  static constexpr bool kKey = true, kSampled = true;
+  AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.enc.rate_mul; }
+  AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.enc.dist_mul; }
+  AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.enc.bmode[above][left]; }
+  AA_MHD static uint32_t mbmode_intra( const Costs & C, int mode ) { return C.enc.mbmode[mode]; }
+  AA_MHD static bool tries_bpred( const Costs & ) { return true; }
+  AA_MHD static int full_mbw( const Costs & C ) { return static_cast<int>( C.full_mbw ); }
+  AA_MHD static int full_mbh( const Costs & C ) { return static_cast<int>( C.full_mbh ); }
+  // the four pixels above-right of a macroblock of the small frame's last column, row >= 1, which no estimate writes (reencode_mb.hh): zero
+  AA_MHD static uint32_t unwritten_pixels( const Costs &, int ) { return 0; }
 };
 
 // luma_sb_intra_predict (encode_intra.cc:360-386): the ten modes ascending, strict <

@@ -42,11 +42,12 @@
 #include "coeff_pack.hh"
 #include "hash_chain.hh"
 #include "reencode_search.hh"
+#include "qi_choose.hh"
 #include "rebase_compact.hh"
 #include "reencode_compact.hh"
 #include "serializer.hh"
 
-// ONE translation unit, this file and the fifteen it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
+// ONE translation unit, this file and the sixteen it #includes (the reference does the same: macroblock.cc #includes tokens.cc, transform.cc, ...):
 // the pieces share file-local state (the anonymous-namespace helpers, g_last_error) and are #included in dependency order.
 #include "runtime_types.inc"
 #include "runtime_pool.inc"
@@ -63,4 +64,5 @@
 #include "runtime_rebase.inc"
 #include "runtime_reencode.inc"
 #include "runtime_encode.inc"
+#include "runtime_estimate.inc"
 #include "runtime_serialize.inc"

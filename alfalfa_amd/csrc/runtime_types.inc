@@ -235,6 +235,8 @@ struct aa_ctx {
   int lf_round = 4;                         // aa_lf_search_decode_batch: levels per job and round; lf_jobs_per_slice: jobs per slice, 0 = by memory (aa_ctx_set_lf_search_round)
   int lf_jobs_per_slice = 0;
   double lf_timing[8] = {};                 // aa_lf_search_last_timing
+  int target_jobs_per_slice = 0;            // aa_estimate_size_batch / aa_target_size_batch: jobs per slice of a round, 0 = by memory (aa_ctx_set_target_size_round)
+  double target_size_timing[6] = {};        // aa_target_size_last_timing
   JobRing lf_ring;                          // a slice's job table, states and round tables of aa_lf_search_decode_batch, copied on the compute stream into the slice's piece
   JobRing rebase_ring;                     // the job table and input records of a rebase slice (aa_rebase_batch), copied on the compute stream into the slice's piece
   hipEvent_t rgb_consumer_ev = nullptr, quality_consumer_ev = nullptr;   // stream_waits_for: the caller's stream and the compute stream waiting for each other

@@ -289,6 +289,45 @@ size_t assemble_frame( const aa_frame_header & h, const std::vector<uint8_t> & f
   return total;
 }
 
+size_t estimate_frame_bytes( bool key_frame, uint16_t small_w, uint16_t small_h, uint8_t q_index, const uint8_t * probs_before, const aa_mb_info * recs, const uint32_t * masks,
+                             uint32_t token_bytes, uint32_t with_coefficients, uint32_t intra, uint8_t carry[4] )
+{
+  aa_frame_header h;
+  std::memset( &h, 0, sizeof h );
+  h.key_frame = key_frame; h.show_frame = 1; h.num_dct_partitions = 1; h.q_index = q_index;
+  h.refresh_last = 1; h.refresh_golden = h.refresh_alternate = key_frame;
+  h.width = small_w; h.height = small_h;
+  h.mb_width = static_cast<uint16_t>( ( small_w + 15 ) / 16 ); h.mb_height = static_cast<uint16_t>( ( small_h + 15 ) / 16 );
+  const uint32_t nmb = static_cast<uint32_t>( h.mb_width ) * h.mb_height;
+  h.num_macroblocks = nmb;
+  std::unique_ptr<aa_frame_header_ext> xp( new aa_frame_header_ext );
+  aa_frame_header_ext & x = *xp;
+  std::memset( &x, 0, sizeof x );
+  x.refresh_entropy_probs = 1;
+  x.skip_enabled = 1; x.prob_skip_false = static_cast<uint8_t>( ser::calc_prob( with_coefficients, nmb ) );          // optimize_prob_skip
+  if ( !key_frame ) {
+    // optimize_interframe_probs (encode_inter.cc:525-575): every inter macroblock is on LAST, so prob_references_golden's count is 0 / 0
+    const uint32_t prob_inter = ser::calc_prob( intra, nmb ), prob_last = ser::calc_prob( nmb - intra, nmb - intra );
+    if ( prob_inter > 0 ) carry[0] = static_cast<uint8_t>( prob_inter );
+    if ( prob_last > 0 ) carry[1] = static_cast<uint8_t>( prob_last );
+    x.prob_inter = carry[0]; x.prob_references_last = carry[1]; x.prob_references_golden = carry[2];
+  }
+  // the records as the first partition reads them: modes, vectors, the inter and the skip flag
+  std::vector<aa_mb_info> mbs( recs, recs + nmb );
+  for ( uint32_t i = 0; i < nmb; i++ ) {
+    aa_mb_info & m = mbs[i];
+    const bool inter = m.ref_frame != 0, y2 = m.y_mode != B_PRED && m.y_mode != SPLITMV;
+    const uint32_t mask = masks[i] & ( y2 ? 0x1FFFFFFu : 0xFFFFFFu );
+    m.flags = static_cast<uint8_t>( ( inter ? AA_MB_INTER : 0u ) | ( y2 ? AA_MB_HAS_Y2 : 0u ) | ( mask ? AA_MB_HAS_NONZERO : AA_MB_SKIP ) );
+    m.nz_mask = mask; m.segment_id = 0;
+  }
+  ProbTables t;
+  frame_probs( probs_before, key_frame, x, t );
+  std::vector<uint8_t> first;
+  write_first_partition( h, x, t, mbs.data(), nullptr, 0, first );
+  return ( key_frame ? 10u : 3u ) + first.size() + token_bytes;
+}
+
 void serialize_frame_host( const aa_frame_header & h, const aa_frame_header_ext & x, const uint8_t * probs_before, const aa_mb_info * mbs, const int16_t * coeffs,
                            const uint8_t * sub_modes, size_t n_sub_modes, std::vector<uint8_t> & out )
 {

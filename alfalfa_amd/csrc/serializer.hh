@@ -35,4 +35,15 @@ size_t assemble_frame( const aa_frame_header & h, const std::vector<uint8_t> & f
 void serialize_frame_host( const aa_frame_header & h, const aa_frame_header_ext & x, const uint8_t * probs_before, const aa_mb_info * mbs, const int16_t * coeffs,
                            const uint8_t * sub_modes, size_t n_sub_modes, std::vector<uint8_t> & out );
 
+// The bytes of an estimate's frame (Encoder::estimate_size, size_estimation.cc): the small frame of small_w x small_h pixels (the
+// original's size / 4, truncated) under a header as the reference's persistent subsampled frame has it -- everything default but y_ac_qi,
+// refresh_entropy_probs, an inter frame's refresh_last, prob_skip_false (optimize_prob_skip: always set) and, an inter frame, the three
+// reference probabilities (optimize_interframe_probs: each only where its new value is above zero, else what the estimate before left:
+// carry[0..2], in and out; a key estimate neither reads nor writes it) -- no token probability update, one DCT partition.  recs / masks: what
+// the decision left (y_mode, uv_mode, ref_frame, u; raw masks); token_bytes, with_coefficients, intra: est::write_tokens' counts;
+// probs_before: the tables before the frame (1101 bytes; a key estimate starts from the defaults and may pass null).
+// -> tag + first partition + the DCT partition.  The estimate is sixteen times this.
+size_t estimate_frame_bytes( bool key_frame, uint16_t small_w, uint16_t small_h, uint8_t q_index, const uint8_t * probs_before, const aa_mb_info * recs, const uint32_t * masks,
+                             uint32_t token_bytes, uint32_t with_coefficients, uint32_t intra, uint8_t carry[4] );
+
 } // namespace aa

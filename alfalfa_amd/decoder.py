@@ -624,6 +624,80 @@ class Context:
         capi.check(self.L.aa_encode_last_timing(self.h, out))
         return dict(zip(("call_ms", "kernels_ms", "download_ms", "records_ms", "append_ms"), out))
 
+    def _size_jobs(self, who, job_type, decoders, targets, key_frame, quality, carry):
+        """estimate_frame_sizes and target_size_q: what their jobs share -> (jobs, what must stay alive)"""
+        n = len(decoders)
+        if len(targets) != n:
+            raise ValueError(who + ": need as many targets as decoders")
+        keys = list(key_frame) if isinstance(key_frame, (list, tuple)) else [key_frame] * n
+        qualities = [quality] * n if isinstance(quality, str) else list(quality)
+        carries = [capi.estimate_carry()] * n if carry is None else ([tuple(carry)] * n if n and not isinstance(carry[0], (list, tuple, np.ndarray)) else [tuple(c) for c in carry])
+        if len(keys) != n or len(qualities) != n or len(carries) != n or any(len(c) != 4 for c in carries):
+            raise ValueError(who + ": key_frame, quality and carry are one for all jobs or one per job; a carry is four bytes")
+        if any(q not in ("best", "rt") for q in qualities):
+            raise ValueError(who + ": quality is \"best\" or \"rt\", one for all jobs or one per job")
+        jobs = (job_type * max(n, 1))()
+        keep = []
+        for i, (d, t) in enumerate(zip(decoders, targets)):
+            t = self._target_planes(who, i, d, t)
+            j = jobs[i]
+            j.stream, j.key_frame, j.quality = d.h, int(bool(keys[i])), (1 if qualities[i] == "rt" else 0)
+            j.target.y, j.target.u, j.target.v = t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr()
+            j.target.y_stride, j.target.uv_stride = t[0].stride(0), t[1].stride(0)
+            j.carry = (C.c_uint8 * 4)(*[int(x) for x in carries[i]])
+            keep.append(t)
+        if n:
+            import torch
+            torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()      # (the targets are ready; the call itself waits for its kernels)
+        return jobs, keep
+
+    def estimate_frame_sizes(self, decoders, targets, q_indices, key_frame=False, quality="best", carry=None):
+        """The frame-size estimate (aa_estimate_size_batch; Encoder::estimate_frame_size, size_estimation.cc: the number xc-enc -y prints as
+        [estimated size=N]), one picture per decoder: targets[i] (as encode_frames takes them) encoded at q_indices[i] (one for all or
+        one per job) as a frame of a quarter of the size in each direction made of every fourth macroblock -- a key estimate where
+        key_frame is set, else predicted from decoders[i]'s current last reference under its current tables -- and that frame's serialised
+        size times 16.  carry: None (aa.estimate_carry()), one for all or one per job: four bytes, see aa_estimate_size_job.
+        -> [(size, carry after)].  Nothing is appended, no decoder changes.  Synchronous."""
+        n = len(decoders)
+        jobs, keep = self._size_jobs("estimate_frame_sizes", capi.EstimateSizeJob, decoders, targets, key_frame, quality, carry)
+        qs = list(q_indices) if isinstance(q_indices, (list, tuple, np.ndarray)) else [q_indices] * n
+        if len(qs) != n:
+            raise ValueError("estimate_frame_sizes: q_indices is one for all jobs or one per job")
+        for i in range(n):
+            jobs[i].q_index = int(qs[i])
+        capi.check(self.L.aa_estimate_size_batch(self.h, jobs, n))
+        return [(int(jobs[i].size_out), tuple(jobs[i].carry)) for i in range(n)]
+
+    def target_size_q(self, decoders, targets, target_sizes, q_lo=4, q_hi=127, key_frame=False, quality="best", carry=None):
+        """The quantiser for a target frame size (aa_target_size_batch; Encoder::encode_with_target_size, encoder.cc:592-629: xc-enc -F),
+        one picture per decoder: the reference's bisection over q_lo..q_hi (aa.target_size_range; one for all or one per job) with
+        estimate_frame_sizes' estimate, all jobs moving together in rounds of one candidate each, at most 7 (8 from a range of all 128 indices).  -> [(q_index, [(q, size)]
+        visited in order, carry after)]; the chosen index goes into the header encode_frames is given.  Nothing is appended, no decoder
+        changes.  Synchronous."""
+        n = len(decoders)
+        jobs, keep = self._size_jobs("target_size_q", capi.TargetSizeJob, decoders, targets, key_frame, quality, carry)
+        sizes = list(target_sizes) if isinstance(target_sizes, (list, tuple, np.ndarray)) else [target_sizes] * n
+        los = list(q_lo) if isinstance(q_lo, (list, tuple)) else [q_lo] * n
+        his = list(q_hi) if isinstance(q_hi, (list, tuple)) else [q_hi] * n
+        if len(sizes) != n or len(los) != n or len(his) != n:
+            raise ValueError("target_size_q: target_sizes, q_lo and q_hi are one for all jobs or one per job")
+        for i in range(n):
+            jobs[i].target_size, jobs[i].q_lo, jobs[i].q_hi = int(sizes[i]), int(los[i]), int(his[i])
+        capi.check(self.L.aa_target_size_batch(self.h, jobs, n))
+        return [(jobs[i].q_index, [(jobs[i].visited_q[k], int(jobs[i].visited_size[k])) for k in range(jobs[i].estimates)], tuple(jobs[i].carry)) for i in range(n)]
+
+    def set_target_size_round(self, jobs_per_slice=0):
+        """Jobs per slice of a round of estimate_frame_sizes / target_size_q (0: by memory) -- aa_ctx_set_target_size_round."""
+        capi.check(self.L.aa_ctx_set_target_size_round(self.h, int(jobs_per_slice)))
+
+    def target_size_timing(self):
+        """The last estimate_frame_sizes or target_size_q of this context (aa_target_size_last_timing), ms: the call (wall clock), then
+        summed over rounds and slices the uploads with the decision kernels, k_estimate_tokens, the results coming down (HIP events),
+        the host's first partitions with the rule (wall clock); and the number of rounds."""
+        out = (C.c_double * 6)()
+        capi.check(self.L.aa_target_size_last_timing(self.h, out))
+        return dict(zip(("call_ms", "decisions_ms", "tokens_ms", "download_ms", "host_ms", "rounds"), out))
+
     def set_reencode_slots(self, slots):
         """Macroblocks of an anti-diagonal per round of the re-encode kernel and of the forward encoder's two (aa_ctx_set_reencode_slots:
         1..16, default 16)."""
@@ -813,6 +887,15 @@ class Decoder:
         """One new frame of this decoder by the forward encoder (Context.encode_frames), a key frame where header["key_frame"] is set ->
         (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]), or with records=False (frame_index, num_coeff_blocks)."""
         return self.ctx.encode_frames([self], [header], [target], quality, append, records)[0]
+
+    def estimate_frame_size(self, target, q_index, key_frame=False, quality="best", carry=None):
+        """The frame-size estimate of one picture against this decoder (Context.estimate_frame_sizes) -> (size, carry after)."""
+        return self.ctx.estimate_frame_sizes([self], [target], [q_index], key_frame, quality, None if carry is None else [carry])[0]
+
+    def target_size_q(self, target, target_size, q_lo=4, q_hi=127, key_frame=False, quality="best", carry=None):
+        """The quantiser index for a target frame size of one picture against this decoder (Context.target_size_q) -> (q_index, [(q, size)]
+        visited, carry after)."""
+        return self.ctx.target_size_q([self], [target], [target_size], q_lo, q_hi, key_frame, quality, None if carry is None else [carry])[0]
 
     def serialize_frame(self, frame_index, header, ext, probs_before=None, advance_state=False, capacity=None, sub_modes=None, optimise=False, details=False):
         """One frame of this decoder, held as records, as VP8 bytes (Context.serialize_frames)."""

@@ -677,6 +677,66 @@ aa_status aa_ctx_set_lf_search_round( aa_ctx * ctx, int levels_per_round, int jo
  * loop filter, [4] the scoring, [5] k_lf_choose and the states down, [6] k_lf_finish and the final filter; [7] the number of rounds. */
 aa_status aa_lf_search_last_timing( aa_ctx * ctx, double out[8] );
 
+/* THE QUANTISER FOR A TARGET FRAME SIZE (Encoder::encode_with_target_size, encoder.cc:592-629: xc-enc -i y4m -F sizes, Salsify's rate
+ * control) and the estimate it bisects over (Encoder::estimate_frame_size, size_estimation.cc: the number xc-enc -y prints as
+ * [estimated size=N]).  An estimate is a complete first-pass encode of every FOURTH macroblock of the picture in each direction as a
+ * frame of uint16( width / 4 ) x uint16( height / 4 ) pixels of its own -- macroblock (c, r) of it encodes the original's (4c, 4r),
+ * searches and predicts at that position of the stream's last reference, takes its census, its clamp, its intra neighbours and the
+ * real-time NEWMV rule from the small frame, and reconstructs at (c, r) -- serialised with one DCT partition, default token
+ * probabilities' updates left out, prob_skip_false and the reference probabilities set as the reference sets them; the estimate is the
+ * frame's size times 16.  k_estimate_key / k_estimate_inter make the decisions (the forward encoder's, on its schedule: a workgroup per
+ * job, aa_ctx_set_reencode_slots caps its rounds), k_estimate_tokens counts the DCT partition's bytes on the device, the host writes
+ * the first partition from the small frame's records.  Neither call appends a frame, advances a DecoderState or touches a reference.
+ *   target     DEVICE planes of the padded size, edge-extended by the caller, as aa_encode_job's.
+ *   key_frame  != 0: a key estimate (default probability tables, no reference, no carry); else the stream's current tables and last
+ *              reference, as aa_encode_batch takes them.
+ *   carry      in and out (an inter estimate; a key estimate leaves it alone).  [0..2]: prob_inter, prob_references_last,
+ *              prob_references_golden of the reference's persistent estimate header -- optimize_interframe_probs replaces each only where
+ *              its new value is above zero, so an estimate without an intra (or without an inter) macroblock is written with what the
+ *              estimate BEFORE it left, across search steps and across frames; a new encoder starts from {0, 0, 0}.  [3] (in): 0 on the
+ *              first inter frame behind a key frame, where the reference's vector cost tables are still all zero (the estimate does not fill
+ *              them; the encode of an inter frame does), else 1: the stream's current motion-vector probabilities, as aa_encode_batch.
+ * aa_target_size_batch moves all jobs together in rounds: one launch over every unfinished job, one candidate each -- the midpoint the
+ * reference would try -- and the rule (qi_choose.hh) continued per job exactly as written there, `estimated_size <= target_size or
+ * ( y_qi_min == y_qi_max and best_y_qi == 255 )` included; at most 7 rounds from the reference's ranges (aa_target_size_range), 8 from 0..127.  No extra candidate is evaluated: the carry makes the
+ * visited sequence part of the result.  Out: q_index, the choice; estimates, their number; visited_q / visited_size, the candidates in
+ * order with their estimates; carry, as the last estimate left it.
+ * One pixel class is the library's own definition: the four pixels above and to the right of the last small-frame column's macroblocks
+ * (rows >= 1) lie in the reference's full-size reconstruction raster beyond anything an estimate writes; here they are 0.
+ * Both calls are synchronous.  Refusals (messages begin with the call's name; a refused call changes nothing and writes no output field):
+ * AA_ERR_ARGUMENT for null pointers, n < 0, a stream of another context or listed twice, q_index / q_lo / q_hi outside 0..127,
+ * q_lo > q_hi, a quality that is none, a row stride smaller than the padded plane's width; AA_ERR_LOGIC for an inter job whose stream's
+ * last reference is not a decoded or imported raster, or whose stream holds a frame appended but not decoded; AA_ERR_UNSUPPORTED for a
+ * display width or height under 4.  n == 0 is AA_OK.  (Still AA_ABI_VERSION 4: an addition.) */
+typedef struct aa_estimate_size_job {
+  aa_stream * stream;
+  aa_quality_ref target;
+  int key_frame, quality /* AA_REENCODE_BEST / AA_REENCODE_REALTIME */, q_index;
+  uint8_t carry[4];            /* in, out */
+  uint64_t size_out;           /* out */
+} aa_estimate_size_job;
+typedef struct aa_target_size_job {
+  aa_stream * stream;
+  aa_quality_ref target;
+  int key_frame, quality, q_lo, q_hi;
+  uint64_t target_size;
+  uint8_t carry[4];            /* in, out */
+  int q_index, estimates;      /* out */
+  int visited_q[8]; uint64_t visited_size[8];   /* out: [0 .. estimates) */
+} aa_target_size_job;
+aa_status aa_estimate_size_batch( aa_ctx * ctx, aa_estimate_size_job * jobs, int n );
+aa_status aa_target_size_batch( aa_ctx * ctx, aa_target_size_job * jobs, int n );
+/* The range the reference's search starts from (encoder.cc:597-608): [4, 127], or last_q - 16 (where that is not below 4) .. last_q + 16
+ * (capped at 127) around the index of the encoder's last frame, which it keeps under real-time quality only.  last_q < 0: none. */
+void aa_target_size_range( int last_q, int * q_lo, int * q_hi );
+/* Jobs per slice of a round (0, the default: as many as a slice of the rebase's scratch bound holds): 1 takes every job through a slice of
+ * its own (tests). */
+aa_status aa_ctx_set_target_size_round( aa_ctx * ctx, int jobs_per_slice );
+/* Where the last successful aa_estimate_size_batch or aa_target_size_batch spent its time, ms: out[0] the whole call (wall clock); summed
+ * over rounds and slices: [1] tables up and the decision kernels, [2] k_estimate_tokens, [3] results down (HIP events on the compute
+ * stream), [4] the host's first partitions and the rule (wall clock); [5] the number of rounds. */
+aa_status aa_target_size_last_timing( aa_ctx * ctx, double out[6] );
+
 /* SERIALISATION (Frame::serialize, serializer.cc:388-829): frame `frame_index` of `stream`, held as records -- parsed from bytes, appended
  * by aa_rebase_batch / aa_reencode_batch / aa_stream_append_records, or device-resident (aa_rebase_device_batch, aa_reencode_device_batch: its 80-byte macroblock
  * records are copied back for the first partition, its blocks never leave HBM) -- becomes a VP8 frame in `out`.  The DCT partitions are written on the
