@@ -11,8 +11,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libalfalfa_amd.so")
-SOURCES = ["parser.cpp", "runtime.cpp", "kernels.hip", "parse_kernels.hip", "quality_kernels.hip", "hash_kernels.hip", "rebase_kernels.hip", "rebase_compact_kernels.hip", "reencode_kernels.hip", "reencode_compact_kernels.hip", "encode_kernels.hip", "estimate_kernels.hip", "serializer.cpp", "serialize_kernels.hip", "lf_search_kernels.hip"]
-HEADERS = ["parser.hh", "bool_reader.hh", "parse_common.hh", "tok_fsm.hh", "coeff_pack.hh", "recon_inl.hh", "runtime_types.inc", "runtime_pool.inc", "runtime_tokens.inc", "runtime_records.inc", "runtime_ctx.inc", "runtime_submit.inc", "runtime_decode.inc", "runtime_rasters.inc", "runtime_hashes.inc", "runtime_quality.inc", "runtime_lf_search.inc", "runtime_lf_batch.inc", "lf_choose.hh", "runtime_rebase.inc", "runtime_reencode.inc", "runtime_encode.inc", "runtime_estimate.inc", "estimate_size.hh", "qi_choose.hh", "runtime_serialize.inc", "serializer.hh", "serialize_common.hh", "bool_writer.hh", "rebase_inl.hh", "rebase_compact.hh", "reencode_compact.hh", "compact_device.hh", "reencode_search.hh", "reencode_mb.hh", "reencode_wave.hh", "reencode_walk.inc", "cost_tables.h", "vp8_tables.h", "vp8_math.hh", "hash_chain.hh", "device_types.h",
+SOURCES = ["parser.cpp", "runtime.cpp", "kernels.hip", "parse_kernels.hip", "quality_kernels.hip", "hash_kernels.hip", "rebase_kernels.hip", "rebase_compact_kernels.hip", "reencode_kernels.hip", "reencode_compact_kernels.hip", "encode_kernels.hip", "encode_two_pass_kernels.hip", "estimate_kernels.hip", "serializer.cpp", "serialize_kernels.hip", "lf_search_kernels.hip"]
+HEADERS = ["parser.hh", "bool_reader.hh", "parse_common.hh", "tok_fsm.hh", "coeff_pack.hh", "recon_inl.hh", "runtime_types.inc", "runtime_pool.inc", "runtime_tokens.inc", "runtime_records.inc", "runtime_ctx.inc", "runtime_submit.inc", "runtime_decode.inc", "runtime_rasters.inc", "runtime_hashes.inc", "runtime_quality.inc", "runtime_lf_search.inc", "runtime_lf_batch.inc", "lf_choose.hh", "runtime_rebase.inc", "runtime_reencode.inc", "runtime_encode.inc", "runtime_estimate.inc", "estimate_size.hh", "qi_choose.hh", "trellis_quant.hh", "key2_first_pass.hh", "runtime_serialize.inc", "serializer.hh", "serialize_common.hh", "bool_writer.hh", "rebase_inl.hh", "rebase_compact.hh", "reencode_compact.hh", "compact_device.hh", "reencode_search.hh", "reencode_mb.hh", "reencode_wave.hh", "reencode_walk.inc", "cost_tables.h", "vp8_tables.h", "vp8_math.hh", "hash_chain.hh", "device_types.h",
            os.path.join("..", "..", "include", "alfalfa_amd.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]

@@ -11,6 +11,7 @@ import numpy as np
 from . import build as _build
 
 AA_OK = 0
+TWO_PASS_UPDATES = 2112      # AA_TWO_PASS_UPDATES: 1056 token_prob_update flags, then 1056 values
 ERR_NAMES = {-1: "Invalid", -2: "Unsupported", -3: "LogicError", -4: "OutOfRange", -5: "HipError",
              -6: "NoDevice", -7: "BadArgument", -8: "NoMemory"}
 
@@ -228,6 +229,9 @@ SYMBOLS = [
     ("aa_ctx_set_reencode_slots", C.c_int, [_P, C.c_int]),
     ("aa_encode_batch", C.c_int, [_P, C.POINTER(ReencodeJob), C.c_int]),
     ("aa_encode_device_batch", C.c_int, [_P, C.POINTER(ReencodeDeviceJob), C.c_int]),
+    ("aa_encode_two_pass_batch", C.c_int, [_P, C.POINTER(ReencodeJob), C.c_int, _P, _P]),
+    ("aa_encode_two_pass_device_batch", C.c_int, [_P, C.POINTER(ReencodeDeviceJob), C.c_int, _P, _P]),
+    ("aa_serialize_two_pass_batch", C.c_int, [_P, C.POINTER(SerializeJob), C.c_int, _P]),
     ("aa_encode_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("aa_estimate_size_batch", C.c_int, [_P, C.POINTER(EstimateSizeJob), C.c_int]), ("aa_target_size_batch", C.c_int, [_P, C.POINTER(TargetSizeJob), C.c_int]),
     ("aa_target_size_range", None, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]), ("aa_ctx_set_target_size_round", C.c_int, [_P, C.c_int]),

@@ -129,6 +129,8 @@ struct aa_serialize_dev_job {
   uint8_t * updates;           // [AA_SERIALIZE_UPDATES]: 1056 update flags, 1056 values, then prob_skip_false, prob_inter, prob_references_last,
                                // prob_references_golden as calc_prob gives them (0: no macroblock on the false side)
   uint8_t probs[1056];         // [4][8][3][11]
+  const uint8_t * first_pass;  // (optimise) null, or [2112]: the update flags and values the FIRST pass of a two-pass key frame left; k_token_probs
+                               // keeps them wherever this pass makes no update (the reference never clears the field between its passes)
 };
 #define AA_SERIALIZE_COUNTS ( 2112 + 8 )
 #define AA_SERIALIZE_UPDATES ( 2112 + 8 )
@@ -262,6 +264,8 @@ int launch_reencode( const aa_reencode_dev_job * jobs, int n, int slots, void * 
 // encode_kernels.hip: the same over jobs of ONE kind of the forward encoder -- key: k_encode_key (costs = EncKeyCosts, no reference read),
 // otherwise k_encode_inter (costs = EncInterCosts)
 int launch_encode( const aa_reencode_dev_job * jobs, int n, bool key, int slots, void * stream );
+// a two-pass key job behind its first pass: k_key2_first_pass, k_key2_updates, k_encode_key2 (encode_two_pass_kernels.hip)
+int launch_encode_second_pass( const aa_reencode_dev_job * jobs, int n, uint32_t max_mbs, int slots, void * stream );
 // estimate_kernels.hip: the same over jobs of ONE kind of the size estimate, whose frames are the small ones -- key: k_estimate_key (costs =
 // EstKeyCosts), otherwise k_estimate_inter (costs = EstInterCosts) -- and, behind them on the same stream, k_estimate_tokens: a lane per job,
 // lanes_per_wave (1..64) to a wave, sizes[i] beside jobs[i]

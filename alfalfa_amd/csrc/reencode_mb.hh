@@ -27,6 +27,49 @@ struct ReencRegs {
   bool nz, nz2;
 };
 
+// The second pass's (Key2Policy; k_encode_key2's lanes and tests/cpp/encode2_sim.cc's): the lane's trellis between its build and its walk
+struct ReencRegs2 : ReencRegs {
+  Trellis tr;
+};
+
+// The Y2 block of a macroblock in the second pass, in the steps the trellis stands between: the forward WHT of the 16 luma DCs (raster
+// order, in LDS) -> c, unquantised; and the decoder's way back from the quantised block -- dequantise, inverse WHT -- to the DC luma
+// block b is reconstructed with (the statements of rebase_inl.hh's y2_block).
+AA_MHD void y2_forward( const int16_t * dcs, int ( &c )[16] )
+{
+  int w1[16];
+#if defined( __HIP_DEVICE_COMPILE__ )
+#pragma unroll
+#endif
+  for ( int i = 0; i < 4; i++ ) { const Quad v = fwht_pass1( dcs[4 * i], dcs[4 * i + 1], dcs[4 * i + 2], dcs[4 * i + 3] ); w1[4 * i] = v.v0; w1[4 * i + 1] = v.v1; w1[4 * i + 2] = v.v2; w1[4 * i + 3] = v.v3; }
+#if defined( __HIP_DEVICE_COMPILE__ )
+#pragma unroll
+#endif
+  for ( int i = 0; i < 4; i++ ) { const Quad v = fwht_pass2( w1[i], w1[i + 4], w1[i + 8], w1[i + 12] ); c[i] = v.v0; c[i + 4] = v.v1; c[i + 8] = v.v2; c[i + 12] = v.v3; }
+}
+AA_MHD int y2_back( const int ( &q2 )[16], const uint16_t * quant, const int b )
+{
+  int c[16], im[16];
+#if defined( __HIP_DEVICE_COMPILE__ )
+#pragma unroll
+#endif
+  for ( int i = 0; i < 16; i++ ) c[i] = dequant( q2[i], i == 0 ? quant[Q_Y2_DC] : quant[Q_Y2_AC] );
+#if defined( __HIP_DEVICE_COMPILE__ )
+#pragma unroll
+#endif
+  for ( int i = 0; i < 4; i++ ) { const Quad v = iwht_pass1( c[i], c[i + 4], c[i + 8], c[i + 12] ); im[i] = v.v0; im[i + 4] = v.v1; im[i + 8] = v.v2; im[i + 12] = v.v3; }
+  int dc_back = 0;
+#if defined( __HIP_DEVICE_COMPILE__ )
+#pragma unroll
+#endif
+  for ( int i = 0; i < 4; i++ ) {
+    const Quad v = iwht_pass2( im[4 * i], im[4 * i + 1], im[4 * i + 2], im[4 * i + 3] );
+    dc_back = b == 4 * i ? v.v0 : dc_back; dc_back = b == 4 * i + 1 ? v.v1 : dc_back;
+    dc_back = b == 4 * i + 2 ? v.v2 : dc_back; dc_back = b == 4 * i + 3 ? v.v3 : dc_back;
+  }
+  return static_cast<int16_t>( dc_back );
+}
+
 // P: whose decision this is (reencode_search.hh) -- the re-encode's, or the forward encoder's for an inter or a key frame
 template <class Lanes, class P = ReencodePolicy>
 struct ReencMb {
@@ -38,6 +81,7 @@ struct ReencMb {
   const size_t mi;
   const int col, row, pw, ph, cw, ch, x0, y0;
   ReencNeighbour above, left;
+  uint32_t above_mask = 0, left_mask = 0;      // the second pass: which blocks of the macroblocks above and to the left hold a coefficient
 
   AA_MHD ReencMb( Lanes & l, const aa_reencode_dev_job & j, ReencLds & s, const size_t m )
     : lanes( l ), RJ( j ), J( j.base ), C( *static_cast<const typename P::Costs *>( j.costs ) ), S( s ), mi( m ), col( static_cast<int>( m % j.base.mbw ) ),
@@ -114,6 +158,55 @@ struct ReencMb {
     } );
     lanes.sync();
   }
+
+  // ---- the second pass: the context of a block's first token = how many of the blocks above and to the left of it hold a coefficient
+  // (Block::context; beyond the frame: none).  own: the macroblock's own blocks as far as they are settled. ----
+  AA_MHD uint32_t y_context( const int b, const uint32_t own ) const
+  {
+    const uint32_t a = b >= 4 ? ( own >> ( b - 4 ) ) & 1u : ( above_mask >> ( 12 + b ) ) & 1u;
+    const uint32_t l = ( b & 3 ) ? ( own >> ( b - 1 ) ) & 1u : ( left_mask >> ( b + 3 ) ) & 1u;
+    return a + l;
+  }
+  // k: 0..7 = plane * 4 + block; own: bit k
+  AA_MHD uint32_t uv_context( const int k, const uint32_t own ) const
+  {
+    const int cb = k & 3;
+    const uint32_t a = cb >= 2 ? ( own >> ( k - 2 ) ) & 1u : ( above_mask >> ( 16 + k + 2 ) ) & 1u;
+    const uint32_t l = ( cb & 1 ) ? ( own >> ( k - 1 ) ) & 1u : ( left_mask >> ( 16 + k + 1 ) ) & 1u;
+    return a + l;
+  }
+  // What the lanes' blocks leave under each context is known (m0, m1, m2: bit k = block k holds a coefficient under context 0, 1, 2):
+  // the blocks in their order, each under the context its settled neighbours give it -> the settled blocks; ctx: block `mine`'s
+  template <class F>
+  AA_MHD static uint32_t settle( const int blocks, const uint32_t m0, const uint32_t m1, const uint32_t m2, const int mine, uint32_t & ctx, F context )
+  {
+    uint32_t own = 0;
+    ctx = 0;
+#if defined( __HIP_DEVICE_COMPILE__ )
+#pragma unroll
+#endif
+    for ( int k = 0; k < 16; k++ ) {
+      if ( k >= blocks ) continue;
+      const uint32_t c = context( k, own );
+      own |= ( ( ( c == 0 ? m0 : ( c == 1 ? m1 : m2 ) ) >> k ) & 1u ) << k;
+      ctx = k == mine ? c : ctx;
+    }
+    return own;
+  }
+  // the lane's trellis is built: bit `at` + 8 * ctx of the result = what its walk leaves under that context
+  template <class Regs>
+  AA_MHD uint32_t outcomes( const Regs & R, const int type, const int at ) const
+  {
+    const TrellisCosts & T = *C.trellis;
+    const bool from0 = R.tr.nonzero_from( 0 ), from1 = R.tr.nonzero_from( 1 );
+    uint32_t v = 0;
+#if defined( __HIP_DEVICE_COMPILE__ )
+#pragma unroll
+#endif
+    for ( uint32_t ctx = 0; ctx < 3; ctx++ ) v |= ( ( R.tr.pick( ctx, type, T, P::rate_mul( C ), P::dist_mul( C ) ) ? from1 : from0 ) ? 1u : 0u ) << ( at + 8 * ctx );
+    return v;
+  }
+  AA_MHD void note_walk( const TrellisTrace & trace ) const { if ( trace.ran && trace.chose_lower ) P::note( C, K2_TRELLIS_NOT_TRUNCATED ); }
 
   // ---- predictions of lane b's units ----
   AA_MHD void predict16( const int mode, const int b, int ( &p )[16] ) const
@@ -234,7 +327,15 @@ struct ReencMb {
 #endif
         for ( int i = 0; i < 16; i++ ) p[i] = S.L.pred[i];
         forward_block( target, J.target_stride[0], p, q );
-        if ( quantize_block( q, J.quant[Q_Y_DC], J.quant[Q_Y_AC] ) ) S.trial_mask |= 1u << sb;
+        if constexpr ( P::kSecondPass ) {
+          // the block's type is the one the FIRST pass ended with (reencode_search.hh): after a 16x16 mode the unquantised DC stays
+          const int type = ( C.first_pass[mi] & 1u ) ? TQ_Y_WITHOUT_Y2 : TQ_Y_AFTER_Y2;
+          TrellisTrace trace;
+          if ( trellis_quantize( q, type, J.quant[Q_Y_DC], J.quant[Q_Y_AC], y_context( sb, S.trial_mask ), *C.trellis, P::rate_mul( C ), P::dist_mul( C ), &trace ) ) S.trial_mask |= 1u << sb;
+          note_walk( trace );
+        } else {
+          if ( quantize_block( q, J.quant[Q_Y_DC], J.quant[Q_Y_AC] ) ) S.trial_mask |= 1u << sb;
+        }
         store_block( J.coeffs + ( mi * 25 + sb ) * 16, q );
         uint32_t rows[4];
         reconstruct_block( q, J.quant[Q_Y_DC], J.quant[Q_Y_AC], false, 0, p, rows );
@@ -274,6 +375,89 @@ struct ReencMb {
     lanes.sync();                                    // (dcs[] is read before the next macroblock of this slot writes it)
     return lanes.sum( []( const int b, ReencRegs & R ) { return ( R.nz ? 1u << b : 0u ) | ( b == 0 && R.nz2 ? 1u << 24 : 0u ); } );
   }
+  // ... in the second pass (luma_mb_apply_intra_prediction under SECOND_PASS): sixteen trellises built at once, their picks settled in
+  // block order, check_reset_y2 and the Y2 block's own trellis under the Y2 flags of the macroblocks above and to the left
+  AA_MHD uint32_t code_luma_with_y2_second()
+  {
+    using Regs = typename Lanes::Regs;
+    const TrellisCosts & T = *C.trellis;
+    const uint32_t rm = P::rate_mul( C ), dm = P::dist_mul( C );
+    lanes.each( [&]( const int b, Regs & R ) {
+      const int bx = ( b & 3 ) * 4, by = ( b >> 2 ) * 4;
+      forward_block( J.target[0] + static_cast<int64_t>( ty() + by ) * J.target_stride[0] + tx() + bx, J.target_stride[0], R.p, R.q );
+      S.L.dcs[b] = static_cast<int16_t>( R.q[0] );
+      R.q[0] = 0;
+      R.tr.build( R.q, TQ_Y_AFTER_Y2, J.quant[Q_Y_DC], J.quant[Q_Y_AC], T, rm, dm );
+      const uint32_t o = outcomes( R, TQ_Y_AFTER_Y2, 0 );
+      R.s1 = ( ( o & 1u ) << b ) | ( ( ( o >> 8 ) & 1u ) << ( 16 + b ) );
+      R.s0 = static_cast<int32_t>( ( ( o >> 16 ) & 1u ) << b );
+    } );
+    const uint32_t m01 = lanes.sum( []( int, Regs & R ) { return R.s1; } );
+    const uint32_t m2 = lanes.sum( []( int, Regs & R ) { return static_cast<uint32_t>( R.s0 ); } );
+    lanes.each( [&]( const int b, Regs & R ) {
+      uint32_t ctx;
+      settle( 16, m01 & 0xFFFFu, m01 >> 16, m2, b, ctx, [&]( const int k, const uint32_t own ) { return y_context( k, own ); } );
+      TrellisTrace trace;
+      R.nz = R.tr.walk( R.q, R.tr.pick( ctx, TQ_Y_AFTER_Y2, T, rm, dm ), J.quant[Q_Y_DC], J.quant[Q_Y_AC], &trace );
+      note_walk( trace );
+      store_block( J.coeffs + ( mi * 25 + b ) * 16, R.q );
+    } );
+    lanes.sync();
+    // (above.mv / left.mv: the neighbours' side words of the second pass -- bit 0 the Y2 flag they show, bit 1 B_PRED; see run())
+    const uint32_t y2_ctx = ( above.mv & 1u ) + ( left.mv & 1u );
+    lanes.each( [&]( const int b, Regs & R ) {
+      const int bx = ( b & 3 ) * 4, by = ( b >> 2 ) * 4;
+      int q2[16];
+      y2_forward( S.L.dcs, q2 );
+      bool held = false, holds = false;
+      for ( int i = 0; i < 16; i++ ) held |= q2[i] != 0;
+      check_reset_y2( q2, J.quant[Q_Y2_DC], J.quant[Q_Y2_AC] );
+      for ( int i = 0; i < 16; i++ ) holds |= q2[i] != 0;
+      TrellisTrace trace;
+      R.nz2 = trellis_quantize( q2, TQ_Y2, J.quant[Q_Y2_DC], J.quant[Q_Y2_AC], y2_ctx, T, rm, dm, &trace );
+      if ( b == 0 ) {
+        note_walk( trace );
+        if ( held && !holds ) P::note( C, K2_Y2_RESET );
+        if ( trace.ran && ( ( above.mv & 2u ) || ( left.mv & 2u ) ) ) P::note( C, K2_STALE_Y2_CONTEXT );
+        if ( trace.ran && ( ( above.mv & 3u ) == 3u || ( left.mv & 3u ) == 3u ) ) P::note( C, K2_STALE_Y2_SET );
+        store_block( J.coeffs + ( mi * 25 + 24 ) * 16, q2 );
+      }
+      uint32_t rows[4];
+      reconstruct_block( R.q, J.quant[Q_Y_DC], J.quant[Q_Y_AC], true, y2_back( q2, J.quant, b ), R.p, rows );
+      store_rows( J.recon[0] + static_cast<size_t>( y0 + by ) * pw + x0 + bx, pw, rows );
+    } );
+    lanes.sync();                                    // (dcs[] is read before the next macroblock of this slot writes it)
+    return lanes.sum( []( const int b, Regs & R ) { return ( R.nz ? 1u << b : 0u ) | ( b == 0 && R.nz2 ? 1u << 24 : 0u ); } );
+  }
+  // ... and the chroma blocks of the chosen mode (chroma_mb_apply_intra_prediction under SECOND_PASS): lanes 0..7 one block each, U's
+  // and V's picks settled plane by plane -> mask bits 16..23
+  AA_MHD uint32_t code_chroma_second( const int mode )
+  {
+    using Regs = typename Lanes::Regs;
+    const TrellisCosts & T = *C.trellis;
+    const uint32_t rm = P::rate_mul( C ), dm = P::dist_mul( C );
+    const uint32_t m = lanes.sum( [&]( const int b, Regs & R ) {
+      if ( b >= 8 ) return 0u;
+      const int pl = b >> 2, cb = b & 3;
+      predict_chroma( mode, pl, cb, R.p );
+      forward_block( J.target[1 + pl] + static_cast<int64_t>( tcy() + ( cb >> 1 ) * 4 ) * J.target_stride[1] + tcx() + ( cb & 1 ) * 4, J.target_stride[1], R.p, R.q );
+      R.tr.build( R.q, TQ_UV, J.quant[Q_UV_DC], J.quant[Q_UV_AC], T, rm, dm );
+      return outcomes( R, TQ_UV, b ); } );
+    return lanes.sum( [&]( const int b, Regs & R ) {
+      if ( b >= 8 ) return 0u;
+      const int pl = b >> 2, cb = b & 3;
+      uint32_t ctx;
+      settle( 8, m & 0xFFu, ( m >> 8 ) & 0xFFu, ( m >> 16 ) & 0xFFu, b, ctx, [&]( const int k, const uint32_t own ) { return uv_context( k, own ); } );
+      TrellisTrace trace;
+      const bool nz = R.tr.walk( R.q, R.tr.pick( ctx, TQ_UV, T, rm, dm ), J.quant[Q_UV_DC], J.quant[Q_UV_AC], &trace );
+      note_walk( trace );
+      store_block( J.coeffs + ( mi * 25 + 16 + b ) * 16, R.q );
+      uint32_t rows[4];
+      reconstruct_block( R.q, J.quant[Q_UV_DC], J.quant[Q_UV_AC], false, 0, R.p, rows );
+      store_rows( J.recon[1 + pl] + static_cast<size_t>( row * 8 + ( cb >> 1 ) * 4 ) * cw + col * 8 + ( cb & 1 ) * 4, cw, rows );
+      return nz ? 1u << ( 16 + b ) : 0u; } );
+  }
+
   // B_PRED won: its coefficients are in their slots, its reconstruction is in the picture
   AA_MHD uint32_t keep_bpred()
   {
@@ -323,7 +507,8 @@ struct ReencMb {
         return e; } );
     const int mode = pick_uv_mode( sse );
     uv_mode = mode;
-    return lanes.sum( [&]( const int b, ReencRegs & ) {
+    if constexpr ( P::kSecondPass ) return code_chroma_second( mode );
+    else return lanes.sum( [&]( const int b, ReencRegs & ) {
       if ( b >= 8 ) return 0u;
       int p[16];
       predict_chroma( mode, b >> 2, b & 3, p );
@@ -360,6 +545,10 @@ struct ReencMb {
     if ( row > 0 ) above = neighbour( mi - mbw );
     if ( col > 0 ) left = neighbour( mi - 1 );
     if constexpr ( !P::kKey ) { if ( row > 0 && col > 0 ) above_left = neighbour( mi - mbw - 1 ); }      // (a key frame takes no census)
+    if constexpr ( P::kSecondPass ) {
+      if ( row > 0 ) above_mask = load_recon_u32( reinterpret_cast<const uint8_t *>( J.masks + mi - mbw ) );
+      if ( col > 0 ) left_mask = load_recon_u32( reinterpret_cast<const uint8_t *>( J.masks + mi - 1 ) );
+    }
     const ReencCensus cen = [&]() {
       if constexpr ( P::kKey ) return ReencCensus();
       else return census( above, left, above_left, P::inter( C ).mv_counts_to_probs, static_cast<unsigned>( col ), static_cast<unsigned>( row ), mbw, mbh );
@@ -374,7 +563,15 @@ struct ReencMb {
       lanes.each( [&]( const int b, ReencRegs & R ) {
         if constexpr ( P::kKey ) predict16( mode, b, R.p );
         else { if ( inter ) predict_inter( b, choice.mv.x, choice.mv.y, R.p ); else predict16( mode, b, R.p ); } } );
-      mask = code_luma_with_y2( inter, choice.mv );
+      if constexpr ( P::kSecondPass ) mask = code_luma_with_y2_second();
+      else mask = code_luma_with_y2( inter, choice.mv );
+    }
+    // the second pass's side word (a key frame has no vector): bit 0 = the Y2 flag the macroblocks to the right and below see -- this
+    // pass's where a Y2 block is coded, the first pass's where B_PRED leaves the block alone -- and bit 1 = B_PRED
+    uint32_t side_word = 0;
+    if constexpr ( P::kSecondPass ) {
+      side_word = mode == B_PRED ? ( ( C.first_pass[mi] >> 1 ) & 1u ) | 2u : ( mask >> 24 ) & 1u;
+      if ( mode == B_PRED && !( C.first_pass[mi] & 1u ) ) P::note( C, K2_BPRED_AFTER_16X16 );
     }
     if constexpr ( !P::kKey ) mask |= inter ? code_chroma_inter( choice.mv.x, choice.mv.y ) : code_chroma_intra( uv_mode );
     else mask |= code_chroma_intra( uv_mode );
@@ -393,7 +590,8 @@ struct ReencMb {
         rec[1] = 0; rec[2] = mask; rec[3] = 0;
         J.masks[mi] = mask;
         uint32_t * nb = RJ.nb + mi * 4;
-        nb[0] = mvw; nb[1] = inter ? 1u : 0u;
+        if constexpr ( P::kSecondPass ) nb[0] = side_word; else nb[0] = mvw;
+        nb[1] = inter ? 1u : 0u;
         if ( mode < B_PRED ) { nb[2] = implied; nb[3] = implied; }
         else {
           nb[2] = reinterpret_cast<const uint32_t *>( S.bm )[3];

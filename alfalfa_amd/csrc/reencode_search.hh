@@ -11,6 +11,7 @@
 
 #include "cost_tables.h"
 #include "parse_common.hh"
+#include "trellis_quant.hh"
 #include "vp8_math.hh"
 #include "vp8_tables.h"
 
@@ -138,6 +139,7 @@ AA_MHD uint32_t sad_motion_vector_cost( const uint16_t * mv_sad, int mvx, int mv
 struct ReencodePolicy {
   using Costs = ReencCosts;
   static constexpr bool kKey = false, kSampled = false;
+  static constexpr bool kSecondPass = false;
   AA_MHD static uint32_t rate_mul( const Costs & ) { return kRateMultiplier; }
   AA_MHD static uint32_t dist_mul( const Costs & ) { return kDistortionMultiplier; }
   AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.bmode[above][left]; }
@@ -150,6 +152,7 @@ struct ReencodePolicy {
 struct ForwardInterPolicy {
   using Costs = EncInterCosts;
   static constexpr bool kKey = false, kSampled = false;
+  static constexpr bool kSecondPass = false;
   AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.rate_mul; }
   AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.dist_mul; }
   AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.base.bmode[above][left]; }
@@ -163,11 +166,52 @@ struct ForwardInterPolicy {
 struct KeyPolicy {
   using Costs = EncKeyCosts;
   static constexpr bool kKey = true, kSampled = false;
+  static constexpr bool kSecondPass = false;
   AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.rate_mul; }
   AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.dist_mul; }
   AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.bmode[above][left]; }
   AA_MHD static uint32_t mbmode_intra( const Costs & C, int mode ) { return C.mbmode[mode]; }
   AA_MHD static bool tries_bpred( const Costs & ) { return true; }
+};
+
+// aa_encode_two_pass_batch, a key frame's SECOND pass (encode_raster<KeyFrame> with two_pass_encoder_, encode_intra.cc:409-439): the key
+// frame's decision over again, every quantisation the trellis's (trellis_quant.hh) and check_reset_y2 in front of the Y2 block's.  The job's
+// cost block carries, behind the first pass's, the token costs and what the first pass left behind per macroblock (k_key2_first_pass):
+//   bit 0   the first pass chose B_PRED: the type its Y blocks ended with, which the second pass's B_PRED trial meets (the trial quantises
+//           BEFORE it sets the type, encode_intra.cc:62-66) -- after a 16x16 mode the trial's trellis starts at position 1, under the
+//           Y-after-Y2 costs, and leaves the block's unquantised DC where it is
+//   bit 1   the first pass's Y2 block held a coefficient: the flag a macroblock that is B_PRED in the second pass keeps (an uncoded Y2
+//           block is not recomputed, encoder.cc:636), and which the Y2 trellis of the macroblocks to its right and below reads as context
+struct EncKey2Costs {
+  EncKeyCosts enc;
+  const TrellisCosts * trellis;
+  const uint8_t * first_pass;       // [mbw * mbh]
+  uint32_t * counts;                // [2112]: the first pass's branch counts [4][8][3][11][2] {false, true}; zeroed by the host
+  uint8_t * updates;                // [2112]: the first pass's 1056 update flags, then its 1056 values (k_key2_updates)
+  uint32_t * census;                // host simulation only (tests/cpp/encode2_sim.cc): counts of the cases met; null in a job of the kernel's
+};
+static_assert( sizeof( EncKey2Costs ) % 8 == 0, "EncKey2Costs sits in a table of 8-byte aligned pieces" );
+// (the cases the host simulation counts: a walk that kept another level than the truncated quotient or an earlier end; a Y2 block
+// check_reset_y2 emptied; B_PRED chosen after a 16x16 mode of the first pass; a Y2 trellis that ran beside a B_PRED macroblock, whose flag
+// is the first pass's; the same with that flag set)
+enum : int { K2_TRELLIS_NOT_TRUNCATED, K2_Y2_RESET, K2_BPRED_AFTER_16X16, K2_STALE_Y2_CONTEXT, K2_STALE_Y2_SET, K2_CENSUS };
+struct Key2Policy {
+  using Costs = EncKey2Costs;
+  static constexpr bool kKey = true, kSampled = false;
+  static constexpr bool kSecondPass = true;
+  AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.enc.rate_mul; }
+  AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.enc.dist_mul; }
+  AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.enc.bmode[above][left]; }
+  AA_MHD static uint32_t mbmode_intra( const Costs & C, int mode ) { return C.enc.mbmode[mode]; }
+  AA_MHD static bool tries_bpred( const Costs & ) { return true; }
+  AA_MHD static void note( const Costs & C, int what )
+  {
+#if !defined( __HIP_DEVICE_COMPILE__ )
+    if ( C.census ) C.census[what]++;
+#else
+    (void)C; (void)what;
+#endif
+  }
 };
 
 // aa_estimate_size_batch / aa_target_size_batch: Encoder::estimate_size (size_estimation.cc) -- the forward encoder's first pass over
@@ -181,6 +225,7 @@ static_assert( sizeof( EstInterCosts ) % 8 == 0 && sizeof( EstKeyCosts ) % 8 == 
 struct EstimateInterPolicy {
   using Costs = EstInterCosts;
   static constexpr bool kKey = false, kSampled = true;
+  static constexpr bool kSecondPass = false;
   AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.enc.rate_mul; }
   AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.enc.dist_mul; }
   AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.enc.base.bmode[above][left]; }
@@ -196,6 +241,7 @@ struct EstimateInterPolicy {
 struct EstimateKeyPolicy {
   using Costs = EstKeyCosts;
   static constexpr bool kKey = true, kSampled = true;
+  static constexpr bool kSecondPass = false;
   AA_MHD static uint32_t rate_mul( const Costs & C ) { return C.enc.rate_mul; }
   AA_MHD static uint32_t dist_mul( const Costs & C ) { return C.enc.dist_mul; }
   AA_MHD static const uint16_t * bmode( const Costs & C, int above, int left ) { return C.enc.bmode[above][left]; }

@@ -13,9 +13,11 @@ namespace {
 
 constexpr int kReencSlots = 16;                 // macroblocks of an anti-diagonal in flight: 256 lanes
 
-struct DevLanes {
+template <class RegsT>
+struct DevLanesOf {
+  using Regs = RegsT;
   int b;
-  ReencRegs R;
+  RegsT R;
   template <class F> __device__ __forceinline__ void each( F f ) { f( b, R ); }
   template <class F> __device__ __forceinline__ uint32_t sum( F f )
   {
@@ -40,7 +42,8 @@ struct DevLanes {
     __builtin_amdgcn_fence( __ATOMIC_ACQUIRE, "wavefront" );
   }
 };
-
+using DevLanes = DevLanesOf<ReencRegs>;
+using DevLanes2 = DevLanesOf<ReencRegs2>;        // the second pass of a key frame: with the lane's trellis
 
 } // namespace
 } // namespace aa

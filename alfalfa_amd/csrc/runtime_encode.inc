@@ -3,6 +3,9 @@
 // references (encode_raster<InterFrame>), first pass, the header the caller's.  The job checks, the slicing, the cost-block upload, the
 // records, the compaction, the append and the timing are the re-encode's two entries (runtime_reencode.inc), instantiated for this caller:
 // what differs -- key jobs, the forward cost blocks, a kernel per kind (encode_kernels.hip) -- stands there behind Call::kForward.
+// aa_encode_two_pass_batch / aa_encode_two_pass_device_batch: the same calls with, per job, the flag that a KEY job runs the reference's
+// second pass (encode_intra.cc:409-439) behind its first -- k_key2_first_pass, k_key2_updates, k_encode_key2 -- and the first pass's
+// token_prob_update beside the result (TwoPassArgs, runtime_reencode.inc).
 namespace {
 
 struct EncodeCall {
@@ -17,6 +20,19 @@ extern "C" {
 
 aa_status aa_encode_batch( aa_ctx * ctx, aa_encode_job * jobs, int n ) { return reencode_batch<EncodeCall>( ctx, jobs, n ); }
 aa_status aa_encode_device_batch( aa_ctx * ctx, aa_encode_device_job * jobs, int n ) { return reencode_device_batch<EncodeCall>( ctx, jobs, n ); }
+
+aa_status aa_encode_two_pass_batch( aa_ctx * ctx, aa_encode_job * jobs, int n, const uint8_t * two_pass, uint8_t * first_pass_updates )
+{
+  if ( !two_pass || !first_pass_updates ) return fail( AA_ERR_ARGUMENT, "aa_encode_two_pass_batch: null argument" );
+  TwoPassArgs tp; tp.flags = two_pass; tp.updates = first_pass_updates;
+  return reencode_batch<EncodeCall>( ctx, jobs, n, tp );
+}
+aa_status aa_encode_two_pass_device_batch( aa_ctx * ctx, aa_encode_device_job * jobs, int n, const uint8_t * two_pass, uint8_t * first_pass_updates )
+{
+  if ( !two_pass || !first_pass_updates ) return fail( AA_ERR_ARGUMENT, "aa_encode_two_pass_device_batch: null argument" );
+  TwoPassArgs tp; tp.flags = two_pass; tp.updates = first_pass_updates;
+  return reencode_device_batch<EncodeCall>( ctx, jobs, n, tp );
+}
 
 aa_status aa_encode_last_timing( aa_ctx * ctx, double out[5] )
 {

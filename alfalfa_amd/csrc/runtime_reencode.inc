@@ -52,13 +52,49 @@ aa_status reencode_check_job( const char * who, aa_ctx * ctx, const Job * jobs, 
   return AA_OK;
 }
 
+// aa_encode_two_pass_batch / aa_encode_two_pass_device_batch: which jobs of the call are two-pass key jobs (flags, one byte per job) and
+// where each job's first-pass token_prob_update goes (updates, AA_TWO_PASS_UPDATES bytes per job).  Every other call: none.
+struct TwoPassArgs {
+  const uint8_t * flags = nullptr;
+  uint8_t * updates = nullptr;
+  template <class Job> bool two( const Job & j, int i ) const { return flags && flags[i] && j.hdr->key_frame; }
+};
+// A two-pass key job's cost block: EncKey2Costs (whose head is the first pass's EncKeyCosts: one table entry serves k_encode_key and
+// k_encode_key2) | the token costs | the first pass's branch counts | its updates | the macroblocks' side bits
+struct Key2Block {
+  size_t trellis, counts, updates, bits, bytes;
+  explicit Key2Block( size_t nmb )
+  {
+    trellis = align_up( sizeof( aa::EncKey2Costs ) ); counts = trellis + align_up( sizeof( aa::TrellisCosts ) ); updates = counts + align_up( 2112 * sizeof( uint32_t ) );
+    bits = updates + align_up( AA_TWO_PASS_UPDATES ); bytes = bits + align_up( nmb );
+  }
+};
+const aa::TrellisCosts & trellis_costs()
+{
+  static const aa::TrellisCosts T = [] { aa::TrellisCosts t; aa::trellis_fill_costs( t ); return t; }();
+  return T;
+}
+void fill_key2_block( uint8_t * host, uint8_t * dev, size_t nmb, uint16_t y_ac )
+{
+  const Key2Block at( nmb );
+  std::memset( host, 0, at.bytes );
+  aa::EncKey2Costs & C = *reinterpret_cast<aa::EncKey2Costs *>( host );
+  aa::enc_fill_key_costs( C.enc, y_ac );
+  std::memcpy( host + at.trellis, &trellis_costs(), sizeof( aa::TrellisCosts ) );
+  C.trellis = reinterpret_cast<const aa::TrellisCosts *>( dev + at.trellis );
+  C.counts = reinterpret_cast<uint32_t *>( dev + at.counts );
+  C.updates = dev + at.updates;
+  C.first_pass = dev + at.bits;
+  C.census = nullptr;
+}
+
 // Where a slice's kernels find and leave one job's data, in the slice's piece
 struct ReencodePlaces { uint8_t * costs, * masks, * records, * dense, * side, * raster; };
 
 // What a slice's kernels read of one job, into its entry of the job table, its rate model (the pinned copy of *at.costs) and what
 // mb_lf_level reads of it: the new header's level, the stream's current adjustments where the header keeps them switched on
 template <class Call, class Job>
-void reencode_fill_job( aa_reencode_dev_job & d, void * costs, aa::HeaderParams & fp, const Job & j, const ReencodePlaces & at )
+void reencode_fill_job( aa_reencode_dev_job & d, void * costs, aa::HeaderParams & fp, const Job & j, const ReencodePlaces & at, bool two = false )
 {
   aa_stream * s = j.stream;
   const bool key = Call::kForward && j.hdr->key_frame;
@@ -69,6 +105,7 @@ void reencode_fill_job( aa_reencode_dev_job & d, void * costs, aa::HeaderParams 
   // the rate model: the mode costs are constants, the vector costs come from the stream's CURRENT probabilities (reencode.cc:82-84)
   // (the forward encoder adds the job's multipliers and the search's site costs; a key frame's block holds no vector cost at all)
   if ( !Call::kForward ) aa::reenc_fill_costs( *static_cast<aa::ReencCosts *>( costs ), s->parser.probs().mv, j.quality );
+  else if ( key && two ) fill_key2_block( static_cast<uint8_t *>( costs ), at.costs, size_t( j.hdr->mb_width ) * j.hdr->mb_height, j.hdr->quant[0][1] );
   else if ( key ) aa::enc_fill_key_costs( *static_cast<aa::EncKeyCosts *>( costs ), j.hdr->quant[0][1] );
   else aa::enc_fill_inter_costs( *static_cast<aa::EncInterCosts *>( costs ), s->parser.probs().mv, j.quality, j.hdr->quant[0][1], j.hdr->q_index );
   d.costs = at.costs;
@@ -84,32 +121,52 @@ void reencode_fill_job( aa_reencode_dev_job & d, void * costs, aa::HeaderParams 
   aa::compact::lf_params( fp, j.hdr->loop_filter_level, !key && j.hdr->filter_adjustments_enabled && fa.enabled, fa.ref, fa.mode );
 }
 
-// A job's cost block in the slice's upload, and a slice's table order: key jobs first, so that each kernel finds its kind in one run
+// A job's cost block in the slice's upload, and a slice's table order: two-pass key jobs first, then the other key jobs, so that each
+// kernel finds its kind in one run
 template <class Call, class Job>
-size_t reencode_costs_bytes( const Job & j )
+size_t reencode_costs_bytes( const Job & j, bool two = false )
 {
   if ( !Call::kForward ) return align_up( sizeof( aa::ReencCosts ) );
+  if ( two ) return Key2Block( size_t( j.hdr->mb_width ) * j.hdr->mb_height ).bytes;
   return align_up( j.hdr->key_frame ? sizeof( aa::EncKeyCosts ) : sizeof( aa::EncInterCosts ) );
 }
 template <class Call, class Job>
-int reencode_slice_order( const Job * jobs, int first, int count, std::vector<int> & at )
+int reencode_slice_order( const Job * jobs, int first, int count, std::vector<int> & at, const TwoPassArgs & tp = TwoPassArgs(), int * keys2 = nullptr )
 {
   at.clear();
-  if ( Call::kForward ) for ( int k = 0; k < count; k++ ) if ( jobs[first + k].hdr->key_frame ) at.push_back( first + k );
+  if ( Call::kForward ) for ( int k = 0; k < count; k++ ) if ( tp.two( jobs[first + k], first + k ) ) at.push_back( first + k );
+  if ( keys2 ) *keys2 = static_cast<int>( at.size() );
+  if ( Call::kForward ) for ( int k = 0; k < count; k++ ) if ( jobs[first + k].hdr->key_frame && !tp.two( jobs[first + k], first + k ) ) at.push_back( first + k );
   const int keys = static_cast<int>( at.size() );
   for ( int k = 0; k < count; k++ ) if ( !( Call::kForward && jobs[first + k].hdr->key_frame ) ) at.push_back( first + k );
   return keys;
 }
-// The decision over a slice's table: k_reencode_inter, or k_encode_key over its first `keys` entries and k_encode_inter over the rest
+// The decision over a slice's table: k_reencode_inter, or k_encode_key over its first `keys` entries -- behind it, over the first `keys2`
+// of them, what lies between the passes and k_encode_key2 -- and k_encode_inter over the rest
 template <class Call>
-aa_status reencode_launch_decision( aa_ctx * ctx, const aa_reencode_dev_job * table, int count, int keys )
+aa_status reencode_launch_decision( aa_ctx * ctx, const aa_reencode_dev_job * table, int count, int keys, int keys2 = 0, uint32_t max_mbs2 = 0 )
 {
   if ( !Call::kForward ) {
     if ( int e = aa::launch_reencode( table, count, ctx->reenc_slots, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_reencode_inter" );
     return AA_OK;
   }
   if ( keys ) if ( int e = aa::launch_encode( table, keys, true, ctx->reenc_slots, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_encode_key" );
+  if ( keys2 ) if ( int e = aa::launch_encode_second_pass( table, keys2, max_mbs2, ctx->reenc_slots, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_key2_first_pass / k_key2_updates / k_encode_key2" );
   if ( count > keys ) if ( int e = aa::launch_encode( table + keys, count - keys, false, ctx->reenc_slots, ctx->compute ) ) return hip_fail( static_cast<hipError_t>( e ), "k_encode_inter" );
+  return AA_OK;
+}
+// The first pass's updates of a slice's two-pass jobs (its first keys2 table entries) into the caller's array, queued behind the kernels;
+// every other job's entry is zero: no update
+template <class Job>
+aa_status reencode_fetch_updates( aa_ctx * ctx, const TwoPassArgs & tp, const Job * jobs, const std::vector<int> & at_job, int keys2, const std::vector<uint8_t *> & dev_costs )
+{
+  if ( !tp.updates ) return AA_OK;
+  for ( size_t k = 0; k < at_job.size(); k++ ) {
+    uint8_t * out = tp.updates + size_t( at_job[k] ) * AA_TWO_PASS_UPDATES;
+    if ( static_cast<int>( k ) >= keys2 ) { std::memset( out, 0, AA_TWO_PASS_UPDATES ); continue; }
+    const Job & j = jobs[at_job[k]];
+    HIP_TRY( hipMemcpyAsync( out, dev_costs[k] + Key2Block( size_t( j.hdr->mb_width ) * j.hdr->mb_height ).updates, AA_TWO_PASS_UPDATES, hipMemcpyDeviceToHost, ctx->compute ) );
+  }
   return AA_OK;
 }
 
@@ -129,7 +186,7 @@ aa_status aa_ctx_set_reencode_slots( aa_ctx * ctx, int slots )
 namespace {
 
 template <class Call>
-aa_status reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
+aa_status reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n, const TwoPassArgs tp = TwoPassArgs() )
 {
   const std::string who = Call::kHost;
   const auto no = [&who]( aa_status code, int i, const std::string & what ) { return fail( code, who + ": job " + std::to_string( i ) + ": " + what ); };
@@ -157,11 +214,14 @@ aa_status reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
       if ( count && dense_total + nmb * AA_REBASE_MB_BYTES > share ) break;
       dense_total += align_up( nmb * AA_REBASE_MB_BYTES ); masks_total += align_up( nmb * sizeof( uint32_t ) );
       records_total += align_up( nmb * sizeof( aa_mb_info ) ); side_total += align_up( nmb * sizeof( aa::ReencNeighbour ) );
-      raster_total += s->slot_bytes; costs_total += reencode_costs_bytes<Call>( jobs[first + count] );
+      raster_total += s->slot_bytes; costs_total += reencode_costs_bytes<Call>( jobs[first + count], tp.two( jobs[first + count], first + count ) );
       count++;
     }
     std::vector<int> at_job;                     // table entry -> job of the call
-    const int keys = reencode_slice_order<Call>( jobs, first, count, at_job );
+    int keys2 = 0;
+    const int keys = reencode_slice_order<Call>( jobs, first, count, at_job, tp, &keys2 );
+    std::vector<uint8_t *> dev_costs( count );   // a table entry's cost block on the device
+    uint32_t max_mbs2 = 0;                       // the largest frame among the two-pass jobs
     // the pinned side: job table | every job's rate model (a JobRing entry, read by one copy); the device piece: the same, then per job
     // masks | records | dense coefficients (the results, downloaded by one copy), then side records and reconstruction rasters
     const size_t table_bytes = align_up( size_t( count ) * sizeof( aa_reencode_dev_job ) );
@@ -193,8 +253,10 @@ aa_status reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
       at.dense = piece + up_bytes + res_off; res_off += align_up( nmb * AA_REBASE_MB_BYTES );
       at.side = piece + side_off; side_off += align_up( nmb * sizeof( aa::ReencNeighbour ) );
       at.raster = piece + side_off; side_off += s->slot_bytes;
-      reencode_fill_job<Call>( table[k], rb->host + up_off, lf_params[k], j, at );
-      up_off += reencode_costs_bytes<Call>( j );
+      dev_costs[k] = at.costs;
+      if ( k < keys2 ) max_mbs2 = std::max<uint32_t>( max_mbs2, static_cast<uint32_t>( nmb ) );
+      reencode_fill_job<Call>( table[k], rb->host + up_off, lf_params[k], j, at, k < keys2 );
+      up_off += reencode_costs_bytes<Call>( j, k < keys2 );
     }
     hipEvent_t ev[3] = { get_event( ctx ), get_event( ctx ), get_event( ctx ) };      // (aa_reencode_last_timing: tables up + kernel, results down)
     struct Events { aa_ctx * c; hipEvent_t * e; ~Events() { for ( int i = 0; i < 3; i++ ) if ( e[i] ) c->free_events.push_back( e[i] ); } } events { ctx, ev };
@@ -202,8 +264,9 @@ aa_status reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
     HIP_TRY( hipEventRecord( ev[0], ctx->compute ) );
     HIP_TRY( hipMemcpyAsync( piece, rb->host, up_bytes, hipMemcpyHostToDevice, ctx->compute ) );
     if ( aa_status st = ctx->rebase_ring.mark( *rb, ctx->compute ) ) return st;
-    if ( aa_status st = reencode_launch_decision<Call>( ctx, reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, keys ) ) return st;
+    if ( aa_status st = reencode_launch_decision<Call>( ctx, reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, keys, keys2, max_mbs2 ) ) return st;
     HIP_TRY( hipEventRecord( ev[1], ctx->compute ) );
+    if ( aa_status st = reencode_fetch_updates( ctx, tp, jobs, at_job, keys2, dev_costs ) ) return st;
     HIP_TRY( hipMemcpyAsync( staging, piece + up_bytes, result_bytes, hipMemcpyDeviceToHost, ctx->compute ) );
     HIP_TRY( hipEventRecord( ev[2], ctx->compute ) );
     HIP_TRY( hipStreamSynchronize( ctx->compute ) );
@@ -287,7 +350,7 @@ aa_status reencode_batch( aa_ctx * ctx, aa_reencode_job * jobs, int n )
  * device-rebased frame's: no chunk, no batch, rec_block = the piece (job record | macroblock records | intra-row words | dense
  * blocks), dev_job = its start. */
 template <class Call>
-aa_status reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs, int n )
+aa_status reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs, int n, const TwoPassArgs tp = TwoPassArgs() )
 {
   const std::string who = Call::kDevice;
   if ( !ctx || !jobs || n <= 0 ) return fail( AA_ERR_ARGUMENT, who + ": bad argument" );
@@ -322,12 +385,15 @@ aa_status reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs, in
       dense_total += align_up( nmb * AA_REBASE_MB_BYTES ); masks_total += align_up( nmb * sizeof( uint32_t ) );
       records_total += align_up( nmb * sizeof( aa_mb_info ) ); side_total += align_up( nmb * sizeof( aa::ReencNeighbour ) );
       rows_total += align_up( size_t( aa::compact::row_words( s->parser.mb_width(), s->parser.mb_height() ) ) * sizeof( unsigned long long ) );
-      raster_total += s->slot_bytes; costs_total += reencode_costs_bytes<Call>( jobs[first + count] );
+      raster_total += s->slot_bytes; costs_total += reencode_costs_bytes<Call>( jobs[first + count], tp.two( jobs[first + count], first + count ) );
       max_mbs = std::max<uint32_t>( max_mbs, static_cast<uint32_t>( nmb ) );
       count++;
     }
     std::vector<int> at_job;                     // table entry -> job of the call
-    const int keys = reencode_slice_order<Call>( jobs, first, count, at_job );
+    int keys2 = 0;
+    const int keys = reencode_slice_order<Call>( jobs, first, count, at_job, tp, &keys2 );
+    std::vector<uint8_t *> dev_costs( count );   // a table entry's cost block on the device
+    uint32_t max_mbs2 = 0;                       // the largest frame among the two-pass jobs
     // the slice's piece: job table | rate models (one upload) | compaction table | filter-level parameters (a second one, once the
     // pieces are known) | partial sums | intra-row words (one download) | masks | records | dense slots | side records | reconstruction
     // rasters.  Pinned: a JobRing entry for each upload; the download lands behind the first one's table.
@@ -367,8 +433,10 @@ aa_status reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs, in
       at.dense = results + res_off; res_off += align_up( nmb * AA_REBASE_MB_BYTES );
       at.side = piece + side_off; side_off += align_up( nmb * sizeof( aa::ReencNeighbour ) );
       at.raster = piece + side_off; side_off += s->slot_bytes;
-      reencode_fill_job<Call>( table[k], rb->host + up_off, lf_params[k], j, at );
-      up_off += reencode_costs_bytes<Call>( j );
+      dev_costs[k] = at.costs;
+      if ( k < keys2 ) max_mbs2 = std::max<uint32_t>( max_mbs2, static_cast<uint32_t>( nmb ) );
+      reencode_fill_job<Call>( table[k], rb->host + up_off, lf_params[k], j, at, k < keys2 );
+      up_off += reencode_costs_bytes<Call>( j, k < keys2 );
       const uint32_t words = aa::compact::row_words( j.hdr->mb_width, j.hdr->mb_height );
       table[k].intra_rows = reinterpret_cast<unsigned long long *>( down_dev + rows_off );
       rows_at[k] = rows_off;
@@ -383,7 +451,8 @@ aa_status reencode_device_batch( aa_ctx * ctx, aa_reencode_device_job * jobs, in
     if ( !ev[0] || !ev[1] || !ev[2] || !ev[3] || !ev[4] ) return fail( AA_ERR_HIP, who + ": hipEventCreate failed" );
     HIP_TRY( hipEventRecord( ev[0], ctx->compute ) );
     HIP_TRY( hipMemcpyAsync( piece, rb->host, up_bytes, hipMemcpyHostToDevice, ctx->compute ) );
-    if ( aa_status st = reencode_launch_decision<Call>( ctx, reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, keys ) ) return st;
+    if ( aa_status st = reencode_launch_decision<Call>( ctx, reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, keys, keys2, max_mbs2 ) ) return st;
+    if ( aa_status st = reencode_fetch_updates( ctx, tp, jobs, at_job, keys2, dev_costs ) ) return st;
     if ( int e = aa::launch_reencode_count( reinterpret_cast<const aa_reencode_dev_job *>( piece ), count, max_mbs, partials_dev, stride, ctx->compute ) )
       return hip_fail( static_cast<hipError_t>( e ), "k_reencode_count" );
     HIP_TRY( hipEventRecord( ev[1], ctx->compute ) );

@@ -65,7 +65,13 @@ aa_status aa_stream_last_sub_modes( const aa_stream * s, uint8_t * out, size_t c
 
 static_assert( sizeof( aa_frame_header_ext ) == 2258, "aa_frame_header_ext is bytes only: the bindings mirror it field by field" );
 
-aa_status aa_serialize_batch( aa_ctx * ctx, aa_serialize_job * jobs, int n )
+} // extern "C"
+
+namespace {
+
+// aa_serialize_batch; first_pass (aa_serialize_two_pass_batch, else null): [n][AA_TWO_PASS_UPDATES], the update tables the first pass of a
+// two-pass key frame left (aa_encode_two_pass_batch), which an optimising job keeps wherever its own pass makes no update
+aa_status serialize_batch( aa_ctx * ctx, aa_serialize_job * jobs, int n, const uint8_t * first_pass )
 {
   const auto no = []( aa_status code, int i, const std::string & what ) { return fail( code, "aa_serialize_batch: job " + std::to_string( i ) + ": " + what ); };
   if ( !ctx || !jobs || n <= 0 ) return fail( AA_ERR_ARGUMENT, "aa_serialize_batch: bad argument" );
@@ -144,7 +150,8 @@ aa_status aa_serialize_batch( aa_ctx * ctx, aa_serialize_job * jobs, int n )
   const size_t table_bytes = align_up( size_t( n ) * sizeof( aa_serialize_dev_job ) ), lanes_bytes = align_up( n_lanes * sizeof( uint32_t ) );
   const size_t sizes_bytes = align_up( size_t( n ) * 8 * sizeof( uint32_t ) );
   const size_t counts_bytes = any_optimise ? align_up( size_t( n ) * AA_SERIALIZE_COUNTS * sizeof( uint32_t ) ) : 0, updates_bytes = any_optimise ? align_up( size_t( n ) * AA_SERIALIZE_UPDATES ) : 0;
-  const size_t up_bytes = table_bytes + lanes_bytes, piece_bytes = up_bytes + sizes_bytes + counts_bytes + updates_bytes + align_up( staging_total );
+  const size_t first_bytes = first_pass && any_optimise ? align_up( size_t( n ) * AA_TWO_PASS_UPDATES ) : 0;
+  const size_t up_bytes = table_bytes + lanes_bytes + first_bytes, piece_bytes = up_bytes + sizes_bytes + counts_bytes + updates_bytes + align_up( staging_total );
   JobRing::Entry * rb = nullptr;
   if ( aa_status st = ctx->rebase_ring.take( up_bytes, align_up( 64 * sizeof( aa_rebase_dev_job ) ), &rb ) ) return st;
   uint8_t * piece = nullptr;
@@ -164,9 +171,11 @@ aa_status aa_serialize_batch( aa_ctx * ctx, aa_serialize_job * jobs, int n )
     d.optimise = jobs[i].optimise != 0;
     d.skip_enabled = d.optimise || exts[i].skip_enabled != 0;          // (optimize_prob_skip always sets prob_skip_false)
     if ( d.optimise ) { d.counts = reinterpret_cast<uint32_t *>( dev_counts ) + size_t( i ) * AA_SERIALIZE_COUNTS; d.updates = dev_updates + size_t( i ) * AA_SERIALIZE_UPDATES; }
+    if ( d.optimise && first_bytes ) d.first_pass = piece + table_bytes + lanes_bytes + size_t( i ) * AA_TWO_PASS_UPDATES;
     std::memcpy( d.probs, tables[i].coeff, 1056 );
     for ( unsigned p = 0; p < d.nparts; p++ ) lanes[lane++] = static_cast<uint32_t>( i ) << 3 | p;
   }
+  if ( first_bytes ) std::memcpy( rb->host + table_bytes + lanes_bytes, first_pass, size_t( n ) * AA_TWO_PASS_UPDATES );
   // a wave is bound by its instruction issue and its lanes diverge: every SIMD gets a wave before any wave gets a second lane
   int cus = 0;
   const int simds = hipDeviceGetAttribute( &cus, hipDeviceAttributeMultiprocessorCount, ctx->device ) == hipSuccess && cus > 0 ? 4 * cus : 1024;
@@ -332,6 +341,17 @@ aa_status aa_serialize_batch( aa_ctx * ctx, aa_serialize_job * jobs, int n )
   const double timing[5] = { t_end - t_call, ms_kernel, ms_down, ms_first, t_end - t_assemble };
   std::memcpy( ctx->serialize_timing, timing, sizeof timing );
   return AA_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+aa_status aa_serialize_batch( aa_ctx * ctx, aa_serialize_job * jobs, int n ) { return serialize_batch( ctx, jobs, n, nullptr ); }
+aa_status aa_serialize_two_pass_batch( aa_ctx * ctx, aa_serialize_job * jobs, int n, const uint8_t * first_pass_updates )
+{
+  if ( !first_pass_updates ) return fail( AA_ERR_ARGUMENT, "aa_serialize_two_pass_batch: null argument" );
+  return serialize_batch( ctx, jobs, n, first_pass_updates );
 }
 
 aa_status aa_serialize_host( const aa_frame_header * hdr, const aa_frame_header_ext * ext, const uint8_t * probs_before, const aa_mb_info * mbs,

@@ -113,8 +113,9 @@ __global__ __launch_bounds__( 256 ) void k_token_probs( aa_serialize_dev_job * j
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   const uint32_t * c = J.counts;
   if ( i < 1056 ) {
-    const uint32_t prob = ser::calc_prob( c[2 * i], c[2 * i] + c[2 * i + 1] );
-    const bool update = prob > 0 && prob != J.probs[i];
+    uint32_t prob = ser::calc_prob( c[2 * i], c[2 * i] + c[2 * i + 1] );
+    bool update = prob > 0 && prob != J.probs[i];
+    if ( !update && J.first_pass && J.first_pass[i] ) { update = true; prob = J.first_pass[1056 + i]; }      // (a two-pass key frame: the first pass's update stands)
     J.updates[i] = update; J.updates[1056 + i] = update ? static_cast<uint8_t>( prob ) : 0;
     if ( update ) J.probs[i] = static_cast<uint8_t>( prob );
   } else if ( i == 1056 ) J.updates[2112] = static_cast<uint8_t>( ser::calc_prob( c[2112], static_cast<uint32_t>( J.frame->mbw ) * J.frame->mbh ) );   // optimize_prob_skip

@@ -496,7 +496,7 @@ class Context:
         with append=False this raises ValueError."""
         return self._decide_frames("reencode_as_inter", self.L.aa_reencode_batch, self.L.aa_reencode_device_batch, decoders, headers, targets, quality, append, records)
 
-    def encode_frames(self, decoders, headers, targets, quality="best", append=True, records=True):
+    def encode_frames(self, decoders, headers, targets, quality="best", append=True, records=True, two_pass=False):
         """The forward encoder (aa_encode_batch; Encoder::encode_with_quantizer, encoder.cc:559-575: xc-enc -i y4m -y QI -q best|rt), one
         new frame per decoder: targets[i] encoded as a key frame where headers[i]["key_frame"] is set (encode_raster<KeyFrame>; needs
         no reference and no earlier frame) and otherwise as an inter frame predicted from decoders[i]'s current last reference
@@ -506,11 +506,28 @@ class Context:
         (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]) as reencode_as_inter returns them; with append False nothing is appended
         and frame_index is -1.  The frames go on to lf_search_decode / decode_batch and serialize_frames( optimise=True ).  Synchronous.
         records=False (aa_encode_device_batch): the new frame's records are compacted on the device and stay there -- the result per
-        job is (frame_index, num_coeff_blocks).  Such a frame is always appended: together with append=False this raises ValueError."""
-        return self._decide_frames("encode_frames", self.L.aa_encode_batch, self.L.aa_encode_device_batch, decoders, headers, targets, quality, append, records)
+        job is (frame_index, num_coeff_blocks).  Such a frame is always appended: together with append=False this raises ValueError.
+        two_pass (one flag or one per job; aa_encode_two_pass_batch / aa_encode_two_pass_device_batch: xc-enc --two-pass): a KEY job
+        whose flag is set runs the reference's second pass behind the first -- the decision again with trellis quantisation and
+        check_reset_y2 (encode_intra.cc:409-439) -- and its records are the second pass's; inter jobs are untouched.  Where any flag is
+        set every job's result has one more element: the FIRST pass's token_prob_update, uint8 [2112] (1056 flags, 1056 values; zero
+        for a job without a second pass), which serialize_frames( optimise=True, first_pass_updates=... ) keeps wherever the second
+        pass makes no update, as the reference does.  With no flag set the call and its results are exactly those without the argument."""
+        flags = [bool(f) for f in two_pass] if isinstance(two_pass, (list, tuple, np.ndarray)) else [bool(two_pass)] * len(decoders)
+        if len(flags) != len(decoders):
+            raise ValueError("encode_frames: two_pass is one flag or one per job")
+        if not any(flags):
+            return self._decide_frames("encode_frames", self.L.aa_encode_batch, self.L.aa_encode_device_batch, decoders, headers, targets, quality, append, records)
+        n = len(decoders)
+        which = np.array(flags, dtype=np.uint8)
+        updates = np.zeros((n, capi.TWO_PASS_UPDATES), dtype=np.uint8)
+        extra = (which.ctypes.data_as(C.c_void_p), updates.ctypes.data_as(C.c_void_p))
+        out = self._decide_frames("encode_frames", self.L.aa_encode_two_pass_batch, self.L.aa_encode_two_pass_device_batch, decoders, headers, targets, quality, append,
+                                  records, extra)
+        return [r + (updates[i].copy(),) for i, r in enumerate(out)]
 
-    def _decide_frames(self, who, host_call, device_call, decoders, headers, targets, quality, append, records):
-        """reencode_as_inter and encode_frames: the same jobs into two pairs of ABI calls."""
+    def _decide_frames(self, who, host_call, device_call, decoders, headers, targets, quality, append, records, extra=()):
+        """reencode_as_inter and encode_frames: the same jobs into two pairs of ABI calls (extra: what a call takes behind its jobs)."""
         import torch
         n = len(decoders)
         if n == 0 or len(headers) != n or len(targets) != n:
@@ -532,7 +549,7 @@ class Context:
                 j.target.y_stride, j.target.uv_stride = t[0].stride(0), t[1].stride(0)
                 keep.append((hdr, t))
             torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
-            capi.check(device_call(self.h, jobs, n))
+            capi.check(device_call(self.h, jobs, n, *extra))
             return [(jobs[i].frame_index, jobs[i].num_coeff_blocks) for i in range(n)]
         jobs = (capi.ReencodeJob * n)()
         keep, outs = [], []
@@ -551,10 +568,11 @@ class Context:
             keep.append((hdr, t))
             outs.append((mb_out, cf, hdr.mb_width, hdr.mb_height))
         torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()      # (the targets are ready; the call itself waits for its kernel)
-        capi.check(host_call(self.h, jobs, n))
+        capi.check(host_call(self.h, jobs, n, *extra))
         return [(jobs[i].frame_index, mb_out.reshape(mbh, mbw), cf[:jobs[i].num_coeff_blocks].copy()) for i, (mb_out, cf, mbw, mbh) in enumerate(outs)]
 
-    def serialize_frames(self, decoders, frame_indices, headers, exts, probs_before=None, advance_state=False, capacity=None, optimise=False, sub_modes=None, details=False):
+    def serialize_frames(self, decoders, frame_indices, headers, exts, probs_before=None, advance_state=False, capacity=None, optimise=False, sub_modes=None, details=False,
+                         first_pass_updates=None):
         """The serialisation (aa_serialize_batch; Frame::serialize, serializer.cc:388-829): frame frame_indices[i] of decoders[i], held as
         records (parsed, rebased, re-encoded or appended), written as a VP8 frame with the header headers[i] (a dict as Parser.parse /
         frame_header return it) and exts[i] (a dict as Parser.header_ext returns it) -- DCT partitions on the GPU, first partition on the
@@ -567,6 +585,9 @@ class Context:
         optimize_interframe_probs, optimize_probability_tables) run on the GPU first and decide prob_skip_false, the three reference
         probabilities and the token probability updates, whatever exts[i] says of them.  -> [bytes], or with details [(bytes, the
         header extension as written, the branch counts the passes used: uint32 [2120], None without optimise)].  Synchronous.
+        first_pass_updates (aa_serialize_two_pass_batch): per job None or the uint8 [2112] encode_frames( two_pass=True ) returned for
+        the frame -- with optimise, wherever the probability pass decides no update the first pass's update is kept, as the reference's
+        two-pass encoder leaves its header; None (for all jobs) is exactly the call without the argument.
         (Decoder.serialize is the decoder's STATE in the reference's format; this is a frame.)"""
         n = len(decoders)
         if n == 0 or len(frame_indices) != n or len(headers) != n or len(exts) != n:
@@ -577,6 +598,18 @@ class Context:
         subs = list(sub_modes) if sub_modes is not None else [None] * n
         if len(before) != n or len(advance) != n or len(caps) != n or len(subs) != n:
             raise ValueError("serialize_frames: per-job arguments must be one per decoder")
+        first = None
+        if first_pass_updates is not None:
+            if len(first_pass_updates) != n:
+                raise ValueError("serialize_frames: first_pass_updates must be one per decoder")
+            first = np.zeros((n, capi.TWO_PASS_UPDATES), dtype=np.uint8)
+            for i, u in enumerate(first_pass_updates):
+                if u is None:
+                    continue
+                u = np.ascontiguousarray(u, dtype=np.uint8).reshape(-1)
+                if len(u) != capi.TWO_PASS_UPDATES:
+                    raise ValueError("serialize_frames: first_pass_updates[%d] holds %d bytes, not %d" % (i, len(u), capi.TWO_PASS_UPDATES))
+                first[i] = u
         jobs = (capi.SerializeJob * n)()
         keep, outs = [], []
         for i, d in enumerate(decoders):
@@ -599,7 +632,10 @@ class Context:
             j.counts_out = None if cnt is None else cnt.ctypes.data_as(C.c_void_p)
             keep.append((hdr, ext, pb, sm, cnt))
             outs.append(out)
-        capi.check(self.L.aa_serialize_batch(self.h, jobs, n))
+        if first is None:
+            capi.check(self.L.aa_serialize_batch(self.h, jobs, n))
+        else:
+            capi.check(self.L.aa_serialize_two_pass_batch(self.h, jobs, n, first.ctypes.data_as(C.c_void_p)))
         if details:
             return [(outs[i][:jobs[i].size].tobytes(), keep[i][1].as_dict(), keep[i][4]) for i in range(n)]
         return [outs[i][:jobs[i].size].tobytes() for i in range(n)]
@@ -883,10 +919,11 @@ class Decoder:
         with records=False (frame_index, num_coeff_blocks)."""
         return self.ctx.reencode_as_inter([self], [header], [target], quality, append, records)[0]
 
-    def encode_frame(self, header, target, quality="best", append=True, records=True):
+    def encode_frame(self, header, target, quality="best", append=True, records=True, two_pass=False):
         """One new frame of this decoder by the forward encoder (Context.encode_frames), a key frame where header["key_frame"] is set ->
-        (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]), or with records=False (frame_index, num_coeff_blocks)."""
-        return self.ctx.encode_frames([self], [header], [target], quality, append, records)[0]
+        (frame_index, mb [mbh, mbw], coeff_blocks [n, 16]), or with records=False (frame_index, num_coeff_blocks); with two_pass (a key
+        frame in the reference's two passes) one more element, the first pass's token_prob_update."""
+        return self.ctx.encode_frames([self], [header], [target], quality, append, records, two_pass)[0]
 
     def estimate_frame_size(self, target, q_index, key_frame=False, quality="best", carry=None):
         """The frame-size estimate of one picture against this decoder (Context.estimate_frame_sizes) -> (size, carry after)."""
@@ -897,10 +934,12 @@ class Decoder:
         visited, carry after)."""
         return self.ctx.target_size_q([self], [target], [target_size], q_lo, q_hi, key_frame, quality, None if carry is None else [carry])[0]
 
-    def serialize_frame(self, frame_index, header, ext, probs_before=None, advance_state=False, capacity=None, sub_modes=None, optimise=False, details=False):
+    def serialize_frame(self, frame_index, header, ext, probs_before=None, advance_state=False, capacity=None, sub_modes=None, optimise=False, details=False,
+                        first_pass_updates=None):
         """One frame of this decoder, held as records, as VP8 bytes (Context.serialize_frames)."""
         return self.ctx.serialize_frames([self], [frame_index], [header], [ext], None if probs_before is None else [probs_before], advance_state, capacity,
-                                         optimise=optimise, sub_modes=None if sub_modes is None else [sub_modes], details=details)[0]
+                                         optimise=optimise, sub_modes=None if sub_modes is None else [sub_modes], details=details,
+                                         first_pass_updates=None if first_pass_updates is None else [first_pass_updates])[0]
 
     def header_ext(self):
         """Parser.header_ext for this decoder's own parser: the frame parse_frame / get_frame_output / submit_frames parsed last."""

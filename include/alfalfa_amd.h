@@ -624,7 +624,25 @@ typedef aa_reencode_job aa_encode_job;
 typedef aa_reencode_device_job aa_encode_device_job;
 aa_status aa_encode_batch( aa_ctx * ctx, aa_encode_job * jobs, int n );
 aa_status aa_encode_device_batch( aa_ctx * ctx, aa_encode_device_job * jobs, int n );
-/* As aa_reencode_last_timing, for the last successful aa_encode_batch or aa_encode_device_batch. */
+/* The forward encoder WITH THE REFERENCE'S SECOND PASS for key frames (xc-enc --two-pass; encode_raster<KeyFrame> with two_pass_encoder_,
+ * encode_intra.cc:409-439): the two calls above with, per job, a flag.  A KEY job whose flag is set runs, behind the first pass
+ * (k_encode_key, unchanged), the decision a second time with every quantisation replaced by Encoder::trellis_quantize and
+ * check_reset_y2 in front of the Y2 block's (k_encode_key2); its records, coefficients and reconstruction are the second pass's.  What
+ * the first pass leaves behind reaches into the second as in the reference: the type its Y blocks ended with, the Y2 flag of a
+ * macroblock that is B_PRED in the second pass, and the header's token_prob_update, which the reference never clears between the passes --
+ * so the call also returns, per job, the FIRST pass's update table, for aa_serialize_batch to keep wherever the second pass makes no
+ * update of its own (aa_serialize_job.first_pass_updates).  The feature is defined for a fresh encoder, as every stream xc-enc writes
+ * has it: the first pass of this frame is the only history.  An inter job, and a key job whose flag is 0, take aa_encode_batch's path
+ * untouched (the reference has no second pass for inter frames, encode_inter.cc:612-622); with every flag 0 the results are
+ * aa_encode_batch's byte for byte.
+ *   two_pass              [n]: job i's flag (ignored for an inter job)
+ *   first_pass_updates    [n][AA_TWO_PASS_UPDATES], out: 1056 update flags then 1056 values ([4][8][3][11], zero where no flag) of job
+ *                         i's first pass; all zero for a job that ran no second pass
+ * Errors as aa_encode_batch's; null arrays are AA_ERR_ARGUMENT.  (Still AA_ABI_VERSION 4: an addition.) */
+#define AA_TWO_PASS_UPDATES 2112
+aa_status aa_encode_two_pass_batch( aa_ctx * ctx, aa_encode_job * jobs, int n, const uint8_t * two_pass, uint8_t * first_pass_updates );
+aa_status aa_encode_two_pass_device_batch( aa_ctx * ctx, aa_encode_device_job * jobs, int n, const uint8_t * two_pass, uint8_t * first_pass_updates );
+/* As aa_reencode_last_timing, for the last successful aa_encode_batch or aa_encode_device_batch (or their two-pass forms). */
 aa_status aa_encode_last_timing( aa_ctx * ctx, double out[5] );
 
 /* THE LOOP-FILTER LEVEL OF APPENDED FRAMES, searched for a whole batch (the last statement of Encoder::reencode_as_interframe,
@@ -785,6 +803,11 @@ typedef struct aa_serialize_job {
   uint32_t * counts_out;
 } aa_serialize_job;
 aa_status aa_serialize_batch( aa_ctx * ctx, aa_serialize_job * jobs, int n );
+/* aa_serialize_batch for frames a two-pass encode made (aa_encode_two_pass_batch): first_pass_updates[n][AA_TWO_PASS_UPDATES] is what that
+ * call returned per job.  A job with optimise keeps, wherever its own probability pass decides no update, the update the first pass made
+ * (Encoder::optimize_probability_tables runs after each pass and never clears the header's token_prob_update, encoder.cc:419-439); a job
+ * whose row is all zero, and a job without optimise, is aa_serialize_batch's.  (Still AA_ABI_VERSION 4: an addition.) */
+aa_status aa_serialize_two_pass_batch( aa_ctx * ctx, aa_serialize_job * jobs, int n, const uint8_t * first_pass_updates );
 /* Where the last successful aa_serialize_batch spent its time, ms: out[0] the whole call (wall clock); [1] job table up and k_serialize_tokens,
  * [2] partition sizes and partitions down (HIP events on the compute stream); [3] the host workers' frame headers and first partitions,
  * [4] assembly, the copy into `out` and the state advance (wall clock; [3] runs beside [1]).  For tools/serialize_probe.py. */

@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""Second-pass fixtures written by the REFERENCE (oracle/_ref/xc-enc = the primary encode of /root/reference/src, compiled in place by the
+committed recipe): under tests/golden/two_pass/
+    <case>.ivf              xc-enc -i y4m -y QI -q best|rt --two-pass over a two-frame clip: frame 0 a key frame encoded in two passes
+                            (encode_intra.cc:409-439: trellis quantisation, check_reset_y2), frame 1 an inter frame predicted from it.
+                            The pictures are tools/make_y4m.synth_frames( w, h, 2, seed, entropy ), which the tests regenerate
+    two_pass_golden.json    per case the geometry, the generator's arguments, the quality and the index
+Every case is also encoded WITHOUT --two-pass (not stored).  Conditions asserted here from the reference's output alone: every case's key
+frame differs from its one-pass twin; at least two cases use an index at which check_reset_y2 is active (a Y2 factor below 35).
+Run in the build container only (needs oracle/_ref and the built package)."""
+import json, os, subprocess, sys, tempfile
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
+import make_y4m
+import alfalfa_amd as aa
+from alfalfa_amd import capi
+
+REF = os.path.join(ROOT, "oracle", "_ref")
+OUT = os.path.join(HERE, "two_pass")
+FRAMES = 2
+#          w    h   seed entropy
+CLIPS = {"16x16": (16, 16, 7, "high"), "72x40": (72, 40, 1, "high"), "80x80": (80, 80, 1, "high"), "80x80low": (80, 80, 2, "low"),
+         "272x272": (272, 272, 2, "low")}
+#         name                 clip        quality  index
+CASES = [("16x16_q93",        "16x16",    "best", 93),
+         ("72x40_q42",        "72x40",    "best", 42),
+         ("72x40_q90",        "72x40",    "best", 90),
+         ("80x80_q45",        "80x80",    "best", 45),
+         ("80x80_q93",        "80x80",    "best", 93),
+         ("80x80_q120",       "80x80",    "best", 120),
+         ("80x80low_q24",     "80x80low", "best", 24),
+         ("80x80low_rt_q30",  "80x80low", "rt",   30),
+         ("272x272_q12",      "272x272",  "best", 12),
+         ("272x272_q18",      "272x272",  "best", 18),
+         ("272x272_q42",      "272x272",  "best", 42)]
+
+
+def main():
+    os.makedirs(OUT, exist_ok=True)
+    enc = os.path.join(REF, "xc-enc")
+    out = {}
+    reset_active = 0
+    with tempfile.TemporaryDirectory() as td:
+        clips = {}
+        for clip, (w, h, seed, ent) in CLIPS.items():
+            clips[clip] = os.path.join(td, clip + ".y4m")
+            make_y4m.write_y4m(clips[clip], w, h, FRAMES, seed, ent)
+        for name, clip, quality, qi in CASES:
+            w, h, seed, ent = CLIPS[clip]
+            ivf, one = os.path.join(OUT, name + ".ivf"), os.path.join(td, "one.ivf")
+            subprocess.run([enc, "-i", "y4m", "-y", str(qi), "-q", quality, "--two-pass", "-o", ivf, clips[clip]], check=True, capture_output=True, text=True)
+            subprocess.run([enc, "-i", "y4m", "-y", str(qi), "-q", quality, "-o", one, clips[clip]], check=True, capture_output=True, text=True)
+            two_frames, one_frames = aa.read_ivf(ivf)[2], aa.read_ivf(one)[2]
+            assert len(two_frames) == FRAMES and len(one_frames) == FRAMES
+            p = aa.Parser(w, h)
+            hdr0 = p.parse(two_frames[0])[0]
+            hdr1 = p.parse(two_frames[1])[0]
+            assert hdr0["key_frame"] and not hdr1["key_frame"] and hdr0["q_index"] == qi
+            assert two_frames[0] != one_frames[0], "%s: the second pass changes nothing in the key frame: the case pins nothing" % name
+            f = capi.quant_factors(qi)
+            active = bool(f[2] < 35 or f[3] < 35)
+            reset_active += active
+            out[name] = {"width": w, "height": h, "seed": seed, "entropy": ent, "quality": quality, "q_index": qi, "check_reset_y2": active}
+            print(name, [len(x) for x in two_frames], "one pass:", [len(x) for x in one_frames], "check_reset_y2 active" if active else "")
+    assert reset_active >= 2, "fewer than two cases use an index at which check_reset_y2 is active"
+    json.dump(out, open(os.path.join(OUT, "two_pass_golden.json"), "w"), indent=1, sort_keys=True)
+
+
+if __name__ == "__main__":
+    main()

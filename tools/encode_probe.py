@@ -8,7 +8,11 @@ same two pictures of ONE stream: the one-picture file gives the key frame's seco
 (processes timed whole: start-up and the reading of the input included, tens of milliseconds beside seconds).  The parent of this call is
 the reference's encoder; it is the yardstick.
 
-    python tools/encode_probe.py [--streams 120] [--copies 4] [--reps 1] [--warmup 0] [--reference] [--device] [--out results.json]
+    python tools/encode_probe.py [--streams 120] [--copies 4] [--reps 1] [--warmup 0] [--reference] [--device] [--two-pass] [--out results.json]
+
+--two-pass: per quality, in the same process, the same KEY pictures on fresh decoders through aa_encode_two_pass_batch (Context.encode_frames(
+two_pass=True ): the reference's second pass with trellis quantisation behind the first); its figures go under "two_pass", beside them the
+ratio of its call to the single-pass key call of the same process.  profiles/encode_two_pass.md holds what was measured.
 
 --device: per quality, in the same process, the same frames on fresh decoders through aa_encode_device_batch (Context.encode_frames(
 records=False ): the records compacted on the device and kept there); its figures go under "device", the download leg being the count
@@ -68,6 +72,7 @@ def main():
     ap.add_argument("--reference", action="store_true", help="also time oracle/_ref/xc-enc on one stream's two pictures")
     ap.add_argument("--out", help="also write the results as JSON to this file")
     ap.add_argument("--device", action="store_true", help="then, per quality, the same frames on fresh decoders through aa_encode_device_batch (records kept in HBM)")
+    ap.add_argument("--two-pass", action="store_true", help="then, per quality, the same key pictures on fresh decoders through aa_encode_two_pass_batch")
     args = ap.parse_args()
     import torch
     import workload
@@ -101,14 +106,15 @@ def main():
     nmb = sum(hh["num_macroblocks"] for hh in b_hdr[0])
     out = {"config": args.config, "frames_per_kind": n, "macroblocks_per_kind": nmb, "reps": args.reps, "qualities": {}}
 
-    def measure(quality, on_device):
-        runs, classes = {"key": [], "inter": []}, {"key": collections.Counter(), "inter": collections.Counter()}
+    def measure(quality, on_device, two_pass=False):
+        kinds = ("key",) if two_pass else ("key", "inter")
+        runs, classes = {kind: [] for kind in kinds}, {kind: collections.Counter() for kind in kinds}
         for rep in range(args.warmup + args.reps):
             decs = [aa.Decoder(ctx, *size) for _ in range(n)]
             ctx.sync()
-            for k, kind in enumerate(("key", "inter")):
+            for k, kind in enumerate(kinds):
                 t0 = time.perf_counter()
-                results = ctx.encode_frames(decs, b_hdr[k], b_t[k], quality=quality, records=not on_device)
+                results = ctx.encode_frames(decs, b_hdr[k], b_t[k], quality=quality, records=not on_device, two_pass=two_pass)
                 wall_py = (time.perf_counter() - t0) * 1e3
                 timing = ctx.encode_timing()
                 timing["python_call_ms"] = wall_py
@@ -129,11 +135,11 @@ def main():
                 del results
                 if rep >= args.warmup:
                     runs[kind].append(timing)
-                print("encode_probe: -q %s %s%s, repetition %d: call %.1f ms" % (quality, kind, ", records kept on the device" if on_device else "", rep, timing["call_ms"]),
+                print("encode_probe: -q %s %s%s%s, repetition %d: call %.1f ms" % (quality, kind, ", two passes" if two_pass else "", ", records kept on the device" if on_device else "", rep, timing["call_ms"]),
                       file=sys.stderr, flush=True)
             del decs
         q = {}
-        for kind in ("key", "inter"):
+        for kind in kinds:
             mean = {leg: float(np.mean([r[leg] for r in runs[kind]])) for leg in LEGS}
             q[kind] = {"runs": runs[kind], "mean": mean, "classes": dict(classes[kind]), "macroblocks_per_s_call": nmb / mean["call_ms"] * 1e3,
                        "frames_per_s_call": n / mean["call_ms"] * 1e3, "ms_per_frame": mean["call_ms"] / n, "share_kernel": mean["kernels_ms"] / mean["call_ms"]}
@@ -142,10 +148,10 @@ def main():
             two = reference_seconds(size[0], size[1], display, headers[0][0]["q_index"], quality)
             if one and two:
                 q["key"]["reference_s_per_frame_one_core"], q["inter"]["reference_s_per_frame_one_core"] = one, two - one
-        for kind in ("key", "inter"):
+        for kind in kinds:
             m, ref = q[kind]["mean"], q[kind].get("reference_s_per_frame_one_core")
-            print("encode -q %s, %s frames%s: %d frames (%d macroblocks): call %.1f ms = up + kernel%s %.1f, download %.1f, host records %.1f, append %.1f; %.2f ms a frame, %.0f frames/s%s; %s"
-                  % (quality, kind, ", records kept on the device," if on_device else "", n, nmb, m["call_ms"], "s" if on_device else "", m["kernels_ms"], m["download_ms"],
+            print("encode -q %s, %s frames%s%s: %d frames (%d macroblocks): call %.1f ms = up + kernel%s %.1f, download %.1f, host records %.1f, append %.1f; %.2f ms a frame, %.0f frames/s%s; %s"
+                  % (quality, kind, ", two passes," if two_pass else "", ", records kept on the device," if on_device else "", n, nmb, m["call_ms"], "s" if on_device else "", m["kernels_ms"], m["download_ms"],
                      m["records_ms"], m["append_ms"], q[kind]["ms_per_frame"], q[kind]["frames_per_s_call"],
                      "; xc-enc on one core: %.2f s a frame" % ref if ref else "", q[kind]["classes"]), flush=True)
         return q
@@ -158,6 +164,14 @@ def main():
                 host = out["qualities"][quality][kind]
                 dev[kind]["coeff_blocks_equal_host_path"] = dev[kind]["runs"][-1]["coeff_blocks"] == host["runs"][-1]["coeff_blocks"]
                 dev[kind]["classes_equal_host_path"] = dev[kind]["classes"] == host["classes"]
+        if args.two_pass:
+            two = out["qualities"][quality]["two_pass"] = measure(quality, False, two_pass=True)
+            two["key"]["call_ratio_to_single_pass"] = two["key"]["mean"]["call_ms"] / out["qualities"][quality]["key"]["mean"]["call_ms"]
+            two["key"]["kernels_ratio_to_single_pass"] = two["key"]["mean"]["kernels_ms"] / out["qualities"][quality]["key"]["mean"]["kernels_ms"]
+            if args.device:
+                dev2 = out["qualities"][quality]["two_pass_device"] = measure(quality, True, two_pass=True)
+                dev2["key"]["call_ratio_to_single_pass"] = dev2["key"]["mean"]["call_ms"] / out["qualities"][quality]["device"]["key"]["mean"]["call_ms"]
+                dev2["key"]["coeff_blocks_equal_host_path"] = dev2["key"]["runs"][-1]["coeff_blocks"] == two["key"]["runs"][-1]["coeff_blocks"]
     print(json.dumps(out))
     if args.out:
         with open(args.out, "w") as f:
