@@ -57,9 +57,10 @@ int encode2_sim_census_words() { return CENSUS_WORDS; }
 // records; updates: 1056 flags then 1056 values, the header's token_prob_update after both passes; census[CENSUS_WORDS]: how often each
 // case the fixtures are meant to hold was met (reencode_search.hh K2_*, then macroblocks whose mode changed between the passes and header
 // fields that survive from the first pass).  scrub != 0: the reconstruction raster is overwritten between the passes -- the second pass
-// reads no pixel the first one wrote, so nothing may change.
-int encode2_sim_frame( int mbw, int mbh, const uint8_t * target, const uint16_t quant[6], aa_mb_info * mbs, int16_t * dense, uint8_t * recon, aa_mb_info * first_mbs,
-                       uint8_t * updates, uint32_t * census, int scrub )
+// reads no pixel the first one wrote, so nothing may change.  first_updates_out (may be null): the FIRST pass's 1056 flags then 1056
+// values, before the merge -- what aa_encode_two_pass_batch hands back for the serialiser.
+int encode2_sim_frame_first( int mbw, int mbh, const uint8_t * target, const uint16_t quant[6], aa_mb_info * mbs, int16_t * dense, uint8_t * recon, aa_mb_info * first_mbs,
+                             uint8_t * updates, uint32_t * census, int scrub, uint8_t * first_updates_out )
 {
   const size_t nmb = size_t( mbw ) * mbh, ysz = nmb * 256, csz = nmb * 64;
   std::vector<uint32_t> masks( nmb, 0 ), nb( nmb * 4, 0 );
@@ -83,6 +84,7 @@ int encode2_sim_frame( int mbw, int mbh, const uint8_t * target, const uint16_t 
   for ( size_t mi = 0; mi < nmb; mi++ ) { bits[mi] = aa::first_pass_bits( mbs[mi], masks[mi] ); first_modes[mi] = mbs[mi].y_mode; }
   if ( first_mbs ) std::memcpy( first_mbs, mbs, nmb * sizeof( aa_mb_info ) );
   updates_of( mbs, masks.data(), dense, mbw, nmb, first_updates.data() );
+  if ( first_updates_out ) std::memcpy( first_updates_out, first_updates.data(), 2112 );
   if ( scrub ) std::memset( recon, 0x5A, nmb * 384 );
   // ---- the second pass ----
   static aa::TrellisCosts T;
@@ -103,6 +105,12 @@ int encode2_sim_frame( int mbw, int mbh, const uint8_t * target, const uint16_t 
   }
   if ( census ) std::memcpy( census, met.data(), CENSUS_WORDS * sizeof( uint32_t ) );
   return 0;
+}
+
+int encode2_sim_frame( int mbw, int mbh, const uint8_t * target, const uint16_t quant[6], aa_mb_info * mbs, int16_t * dense, uint8_t * recon, aa_mb_info * first_mbs,
+                       uint8_t * updates, uint32_t * census, int scrub )
+{
+  return encode2_sim_frame_first( mbw, mbh, target, quant, mbs, dense, recon, first_mbs, updates, census, scrub, nullptr );
 }
 
 } // extern "C"

@@ -7,6 +7,8 @@ committed recipe): under tests/golden/two_pass/
     two_pass_golden.json    per case the geometry, the generator's arguments, the quality and the index
 Every case is also encoded WITHOUT --two-pass (not stored).  Conditions asserted here from the reference's output alone: every case's key
 frame differs from its one-pass twin; at least two cases use an index at which check_reset_y2 is active (a Y2 factor below 35).
+No clip of synth_frames brings the second pass to empty a Y2 block or to choose B_PRED after a 16x16 mode: the fixtures for those cases are
+make_two_pass_crafted_golden.py's, over crafted pictures.
 Run in the build container only (needs oracle/_ref and the built package)."""
 import json, os, subprocess, sys, tempfile
 

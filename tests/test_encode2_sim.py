@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import encode_model as em
 import two_pass_model as tp
 from alfalfa_amd import capi
 from conftest import ROOT
@@ -40,13 +41,15 @@ def built(name, extra):
 def sim_lib():
     L = C.CDLL(built("libencode2_sim.so", ["-O2", "-fPIC", "-shared"]))
     L.encode2_sim_frame.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int]
+    L.encode2_sim_frame_first.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
     assert L.encode2_sim_census_words() == CENSUS_WORDS
     return L
 
 
-def sim_two_pass(L, header, target, scrub=False):
+def sim_two_pass(L, header, target, scrub=False, first_updates=False):
     """One key frame (header: a parsed or made header dict; target: padded planes) through both passes on the host
-    -> (mb [mbh, mbw], dense [mbh, mbw, 25, 16], recon, first-pass mb, updates uint8 [2112], census uint32 [CENSUS_WORDS])"""
+    -> (mb [mbh, mbw], dense [mbh, mbw, 25, 16], recon, first-pass mb, updates uint8 [2112], census uint32 [CENSUS_WORDS]); with
+    first_updates a seventh: the first pass's own updates uint8 [2112], before the merge"""
     mbw, mbh = header["mb_width"], header["mb_height"]
     n = mbw * mbh
     planes = flat(target)
@@ -55,9 +58,11 @@ def sim_two_pass(L, header, target, scrub=False):
     dense = np.zeros((n, 25, 16), np.int16)
     recon = np.zeros(n * 384, np.uint8)
     updates, census = np.zeros(2112, np.uint8), np.zeros(CENSUS_WORDS, np.uint32)
-    assert L.encode2_sim_frame(mbw, mbh, planes.ctypes.data, quant.ctypes.data, mb.ctypes.data, dense.ctypes.data, recon.ctypes.data, first.ctypes.data,
-                               updates.ctypes.data, census.ctypes.data, int(scrub)) == 0
-    return mb.reshape(mbh, mbw), dense.reshape(mbh, mbw, 25, 16), recon, first.reshape(mbh, mbw), updates, census
+    before = np.zeros(2112, np.uint8)
+    assert L.encode2_sim_frame_first(mbw, mbh, planes.ctypes.data, quant.ctypes.data, mb.ctypes.data, dense.ctypes.data, recon.ctypes.data, first.ctypes.data,
+                                     updates.ctypes.data, census.ctypes.data, int(scrub), before.ctypes.data) == 0
+    out = (mb.reshape(mbh, mbw), dense.reshape(mbh, mbw, 25, 16), recon, first.reshape(mbh, mbw), updates, census)
+    return out + (before,) if first_updates else out
 
 
 _sims = {}
@@ -83,7 +88,7 @@ def test_both_passes_equal_the_reference(name):
         assert recon.tobytes() == b"".join(p.tobytes() for p in fr["decoded"]), "%s: the reconstruction is not what the fixture's bytes decode to" % name
 
 
-@pytest.mark.parametrize("name", ["72x40_q90", "80x80_q93", "272x272_q42"])
+@pytest.mark.parametrize("name", ["72x40_q90", "80x80_q93", "272x272_q42", "dot_q40"])
 def test_the_second_pass_reads_no_pixel_of_the_first(name):
     """The reconstruction raster overwritten between the passes: every predictor of the second pass comes from macroblocks it has
     redone itself, so nothing changes."""
@@ -97,21 +102,85 @@ def test_the_census_of_the_fixtures():
     """What the fixtures pin, counted by the host simulation that reproduces them: a macroblock whose mode changes between the passes; a
     block of which the trellis kept another level than the truncated quotient, or an earlier end; a Y2 trellis that ran beside a
     macroblock that is B_PRED in the second pass, whose Y2 flag is the first pass's; a header field that survives from the first pass.
-    Three cases the second pass is written for are met by NO clip of tools/make_y4m up to 272x272 at every third index (and every index
-    up to 21): a Y2 block emptied by check_reset_y2, B_PRED chosen after a 16x16 mode of the first pass -- the second pass only ever
-    moved macroblocks away from B_PRED -- and, which needs the latter, a first-pass Y2 flag that is SET under a B_PRED macroblock.  They are
-    asserted absent here, so that a fixture which does meet one is noticed and the case gets pinned; DESIGN section 7 names them."""
+    Three cases the second pass is written for are met by NO clip of tools/make_y4m.synth_frames up to 272x272 at every third index (and
+    every index up to 21): a Y2 block emptied by check_reset_y2, B_PRED chosen after a 16x16 mode of the first pass -- on those clips the
+    second pass only ever moves macroblocks away from B_PRED -- and, which needs the latter, a first-pass Y2 flag that is SET under a B_PRED
+    macroblock.  They stay asserted absent over SYNTH_CASES; the pictures of tools/make_y4m.crafted reach them, and over CRAFTED_CASES they
+    are asserted present, as tests/golden/make_two_pass_crafted_golden.py asserted when it wrote the fixtures: resets in at least two
+    cases, one of them -q rt; B_PRED after a 16x16 mode in at least three, at an index below 20, between 20 and 60 and above 100; a set
+    stale flag in at least two."""
     total = np.zeros(CENSUS_WORDS, np.uint64)
-    for name in tp.CASES:
+    for name in tp.SYNTH_CASES:
         total += sim_case(name)[5]
     assert total[MODE_CHANGED] > 0 and total[TRELLIS_NOT_TRUNCATED] > 0 and total[STALE_Y2_CONTEXT] > 0 and total[FIELD_SURVIVES] > 0, total.tolist()
-    assert total[Y2_RESET] == 0 and total[BPRED_AFTER_16X16] == 0 and total[STALE_Y2_SET] == 0, "a case DESIGN section 7 lists as unpinned is met: %s" % total.tolist()
+    assert total[Y2_RESET] == 0 and total[BPRED_AFTER_16X16] == 0 and total[STALE_Y2_SET] == 0, "a synth_frames clip meets a case only the crafted pictures were known to: %s" % total.tolist()
     # the index range where check_reset_y2 can act is covered all the same (the reset finds no block to empty there)
-    assert sum(1 for name in tp.CASES if tp.META[name]["check_reset_y2"]) >= 2
+    assert sum(1 for name in tp.SYNTH_CASES if tp.META[name]["check_reset_y2"]) >= 2
+    # the crafted cases: the three cases present
+    assert 6 <= len(tp.CRAFTED_CASES) <= 8
+    met = {name: sim_case(name)[5] for name in tp.CRAFTED_CASES}
+    for name in tp.CRAFTED_CASES:                          # (the counts the make script recorded are the counts of today's model)
+        assert {k: int(met[name][i]) for k, i in (("Y2_RESET", Y2_RESET), ("BPRED_AFTER_16X16", BPRED_AFTER_16X16), ("STALE_Y2_SET", STALE_Y2_SET))} == tp.META[name]["census"], name
+    resets = [name for name in tp.CRAFTED_CASES if met[name][Y2_RESET] > 0]
+    assert len(resets) >= 2 and any(tp.META[name]["quality"] == "rt" for name in resets), resets
+    after = [tp.META[name]["q_index"] for name in tp.CRAFTED_CASES if met[name][BPRED_AFTER_16X16] > 0]
+    assert len(after) >= 3 and any(q < 20 for q in after) and any(20 <= q <= 60 for q in after) and any(q > 100 for q in after), after
+    assert sum(1 for name in tp.CRAFTED_CASES if met[name][STALE_Y2_SET] > 0) >= 2
     # every case's second pass changed something: its key frame differs from the first pass's records
     for name in tp.CASES:
         mb, dense, _, first, _, census = sim_case(name)
-        assert census[MODE_CHANGED] or census[TRELLIS_NOT_TRUNCATED] or census[FIELD_SURVIVES], name
+        assert census[MODE_CHANGED] or census[TRELLIS_NOT_TRUNCATED] or census[FIELD_SURVIVES] or census[Y2_RESET], name
+
+
+def test_the_crafted_pictures_are_the_rule_s():
+    """tools/make_y4m.crafted against the rule written out for single pixels: plain Python integers, one pixel at a time."""
+    import make_y4m
+    w, h = 23, 19
+    for family, amp, cell, base, gx, gy, salt in (("noise", 37, 2, 60, 3, 1, 65), ("checker", 125, 4, 67, 2, 0, 116), ("sparse", 8, 4, 250, 0, 3, 1332), ("dot", 24, 8, 115, 0, 1, 792)):
+        Y, U, V = make_y4m.crafted(w, h, family, amp, cell, base, gx, gy, salt)
+        assert Y.shape == (h, w) and U.shape == V.shape == (10, 12) and (V == 128).all()
+        assert all(U[r, c] == 128 + (r % 2 == 0 and c % 3 == 0) for r in range(10) for c in range(12))
+        for y in range(h):
+            for x in range(w):
+                k = ((x // cell) * 2654435761 ^ (y // cell) * 40503 ^ salt * 97) & 0xffffffff
+                k ^= k >> 13
+                k = k * 0x5bd1e995 & 0xffffffff
+                k ^= k >> 15
+                add = {"noise": k % amp, "checker": ((x // cell + y // cell) & 1) * amp, "sparse": amp if k % 8 == 0 else 0,
+                       "dot": amp if (x % 16) // 4 == 1 and (y % 16) // 4 == 2 else 0}[family]
+                assert Y[y, x] == min(255, max(0, base + gx * x // 4 + gy * y // 4 + add)), (family, x, y)
+        assert all((a == b).all() for f in make_y4m.crafted_frames(w, h, 2, family, amp, cell, base, gx, gy, salt) for a, b in zip(f, (Y, U, V)))
+
+
+# ---- the sweep: tests/golden/two_pass_crafted/sweep.json ----
+_sweep_sims = []
+
+
+def sim_sweep():
+    """Every sweep tuple through the host model -> [(mb, dense, first-pass updates, census)]; once."""
+    if not _sweep_sims:
+        L, s = sim_lib(), tp.sweep()
+        template = tp.case("80x80_q45")["frames"][0]["header"]
+        for t in s["tuples"]:
+            out = sim_two_pass(L, em.header_like(template, s["width"], s["height"], t["q_index"], key=True), tp.sweep_target(t), first_updates=True)
+            _sweep_sims.append((out[0], out[1], out[6], out[5]))
+    return _sweep_sims
+
+
+def test_the_host_model_reproduces_every_digest_of_the_sweep():
+    """The digests are the reference's (the make script took them from xc-enc --two-pass's output); the host model gives every one, and
+    the census sums the make script recorded: the floors it refused to go below are met by the file as it stands."""
+    s = tp.sweep()
+    assert 96 <= len(s["tuples"]) <= 128 and (s["width"], s["height"]) == (64, 64)
+    assert [t["quality"] for t in s["tuples"]] == [("best", "rt")[i % 2] for i in range(len(s["tuples"]))]
+    total = np.zeros(CENSUS_WORDS, np.uint64)
+    for i, (t, (mb, dense, _, census)) in enumerate(zip(s["tuples"], sim_sweep())):
+        assert tp.records_digest(mb, dense) == t["sha256"], "sweep tuple %d %s: the host model's records are not the reference's" % (i, t)
+        assert census[Y2_RESET] or census[BPRED_AFTER_16X16] or census[STALE_Y2_SET], "sweep tuple %d meets none of the three cases" % i
+        total += census
+    got = {"Y2_RESET": int(total[Y2_RESET]), "BPRED_AFTER_16X16": int(total[BPRED_AFTER_16X16]), "STALE_Y2_SET": int(total[STALE_Y2_SET])}
+    assert got == s["census"], (got, s["census"])
+    assert got["Y2_RESET"] >= 100 and got["BPRED_AFTER_16X16"] >= 30 and got["STALE_Y2_SET"] >= 20, got
 
 
 def test_the_same_program_under_the_sanitizers(tmp_path):

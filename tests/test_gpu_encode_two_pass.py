@@ -1,6 +1,7 @@
 """The forward encoder's key frames in the reference's TWO passes on the GPU (aa_encode_two_pass_batch / Context.encode_frames(
 two_pass=True ); needs a real MI355X) against xc-enc -i y4m -y QI -q best|rt --two-pass, bit for bit, on the fixtures of
-tests/golden/two_pass (tests/two_pass_model.py; the same comparison on the host: tests/test_encode2_sim.py).
+tests/golden/two_pass and tests/golden/two_pass_crafted (tests/two_pass_model.py; the same comparison on the host:
+tests/test_encode2_sim.py; the sweep over more crafted pictures: tests/test_gpu_encode_two_pass_crafted.py).
 
 The header of each new frame is the product's parse of the fixture frame (quantiser, loop-filter level, refresh flags); every macroblock's
 modes, b_modes, flags, nz_mask, coeff_index, lf_level and all 25 x 16 coefficients must equal the parse of the fixture frame, the decoded
@@ -160,7 +161,7 @@ def test_560x288_at_16_slots_at_1_slot_and_on_the_host(gpu_ctx):
 
 # ---- 6. device-resident records ----
 def test_records_kept_on_the_device_equal_the_host_record_call(gpu_ctx):
-    names = ["72x40_q90", "80x80_q93", "272x272_q18", "80x80low_rt_q30"]
+    names = ["72x40_q90", "80x80_q93", "272x272_q18", "80x80low_rt_q30", "dot_rt_q26"]      # (the last: B_PRED chosen after a 16x16 mode)
     cases = [tp.case(n) for n in names]
     twins = [[aa.Decoder(gpu_ctx, c["w"], c["h"]) for c in cases] for _ in range(2)]
     headers = [c["frames"][0]["header"] for c in cases]

@@ -32,12 +32,53 @@ def synth_frames(width, height, frames, seed, entropy="low"):
                np.clip(V, 0, 255).astype(np.uint8))
 
 
-def write_y4m(path, width, height, frames, seed, entropy="low", fps=30):
+CRAFTED_FAMILIES = ("noise", "checker", "sparse", "dot")
+
+
+def crafted(width, height, family, amp, cell, base, gx, gy, salt):
+    """A crafted still picture -> (Y, U, V) uint8: a luma ramp (gx, gy: quarter levels per pixel) under one of four textures, flat
+    chroma with one level of ripple.  Integer arithmetic only and no generator state, so that every caller gets the same bytes.  The
+    pictures of synth_frames never bring the reference's second pass to empty a Y2 block or to choose B_PRED after a 16x16 mode; some
+    of these do (tests/golden/make_two_pass_crafted_golden.py)."""
+    assert family in CRAFTED_FAMILIES and amp >= 1 and cell >= 1
+    x = np.arange(width, dtype=np.int64)[None, :]
+    y = np.arange(height, dtype=np.int64)[:, None]
+    hsh = ((x // cell) * 2654435761 ^ (y // cell) * 40503 ^ salt * 97) & 0xffffffff
+    hsh ^= hsh >> 13
+    hsh = hsh * 0x5bd1e995 & 0xffffffff
+    hsh ^= hsh >> 15
+    v = base + gx * x // 4 + gy * y // 4
+    if family == "noise":
+        v = v + hsh % amp
+    elif family == "checker":
+        v = v + ((x // cell + y // cell) & 1) * amp
+    elif family == "sparse":
+        v = v + np.where(hsh % 8 == 0, amp, 0)
+    else:
+        v = v + np.where(((x % 16) // 4 == 1) & ((y % 16) // 4 == 2), amp, 0)
+    Y = np.clip(v, 0, 255).astype(np.uint8)
+    U = np.full(((height + 1) // 2, (width + 1) // 2), 128, np.uint8)
+    V = U.copy()
+    U[::2, ::3] += 1
+    return Y, U, V
+
+
+def crafted_frames(width, height, frames, family, amp, cell, base, gx, gy, salt):
+    """The same crafted picture for every frame index."""
+    for _ in range(frames):
+        yield crafted(width, height, family, amp, cell, base, gx, gy, salt)
+
+
+def write_y4m_frames(path, width, height, pictures, fps=30):
     with open(path, "wb") as f:
         f.write(b"YUV4MPEG2 W%d H%d F%d:1 Ip A1:1 C420jpeg\n" % (width, height, fps))
-        for Y, U, V in synth_frames(width, height, frames, seed, entropy):
+        for Y, U, V in pictures:
             f.write(b"FRAME\n")
             f.write(Y.tobytes()); f.write(U.tobytes()); f.write(V.tobytes())
+
+
+def write_y4m(path, width, height, frames, seed, entropy="low", fps=30):
+    write_y4m_frames(path, width, height, synth_frames(width, height, frames, seed, entropy), fps)
 
 
 if __name__ == "__main__":
